@@ -24,10 +24,17 @@ latency-bound launches run beside another clip's Whisper GEMMs; `ms_per_step` = 
 With N GPUs every rank runs its own clips (weak scaling; config 3: strong); rank 0 makes and PACKS the weights once and all
 ranks receive the packed arena through one RCCL broadcast per model; the hot loop has no collective.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel family (the implicit-GEMM conv/linear kernel):
-algorithmic FLOPs of its launches / their HIP-event durations, measured on the launch stream in an instrumented pass of the
-same step (`frac`), beside the same ratio from the newest committed rocprofv3 summary (`frac_rocprof`).  `cpu_baseline`
-times the oracle (CPU port of the reference path) on one clip of the workload on this host's cores.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, ...);
+`--dump-outputs DIR` then also writes what the last timed step computed (rank 0's waveform) as DIR/<name>.npy, float32 (a fixed, seeded
+sample of the clips when the output exceeds 64 MB); the device RNG is reseeded before the warm-up, so the same arguments give the same
+outputs run after run.
+
+`--full` adds everything beyond the headline figure, each after the timed steps: `config.single_stream` (the same K steps one clip at
+a time), `config.precision_error` of a reduced-precision line, `roofline`, `kernel_time_ms`, `cpu_baseline` + `parity_max_abs_vs_oracle`,
+and the probe-library hooks (SVCMI_TIMELINE / SVCMI_KTRACE_CLOCK).  `roofline` is for the dominant kernel family (the implicit-GEMM
+conv/linear kernel): algorithmic FLOPs of its launches / their HIP-event durations, measured on the launch stream in an instrumented pass
+of the same step (`frac`), beside the same ratio from the newest committed rocprofv3 summary (`frac_rocprof`).  `cpu_baseline` times
+the oracle (CPU port of the reference path) on one clip of the workload on this host's cores.
 """
 import argparse
 import glob
@@ -51,10 +58,33 @@ from workload.stamp import csrc_sha  # noqa: E402
 FP32_MFMA_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: dense fp32 matrix peak (no TF32/xf32 on gfx950)
 BF16_MFMA_PEAK_TFLOPS = 2500.0     # dense bf16 / fp16 matrix peak (the 5 PF headline figure includes 2:1 sparsity)
 HBM_PEAK_GBS = 8000.0
+BENCH_SEED = 20240922            # device RNG seed of the warm-up + timed steps
+DUMP_BYTES = 60_000_000           # --dump-outputs budget (under 64 MB with the .npy headers)
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """``--dump-outputs``: every tensor of ``arrays`` as out_dir/<name>.npy in float32.  An output larger than its share of ``budget``
+    keeps a fixed, seeded sample of its rows (dim 0: the clips), sorted; the rows taken go to out_dir/<name>_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share and a.ndim > 1 and a.shape[0] > 1:
+            k = max(1, int(share // (a.nbytes // a.shape[0] + 8)))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=min(k, a.shape[0]), replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        if a.nbytes > share:       # a single row beyond the budget: a seeded sample of its elements
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share // 12, replace=False))
+            a = a.reshape(-1)[idx]
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        log(f"dump-outputs: {name} {list(a.shape)} float32 -> {os.path.join(out_dir, name + '.npy')}")
 
 
 # ------------------------------------------------------------------------------------------------ workloads
@@ -559,6 +589,13 @@ def main():
                          "for config 1 (config.single_stream then reports the one-clip-at-a-time figure too), 1 otherwise")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-single-stream", action="store_true", help="skip the one-clip-at-a-time timing that accompanies --inflight > 1")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline figure does not need: single-stream timing, "
+                         "precision error of a reduced-precision line, roofline / kernel times, CPU baseline + parity, probe-library hooks "
+                         "(each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB: a fixed, seeded sample of the "
+                         "clips beyond that)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: the launch contract of a multi-rank job end to end on CPU over gloo -- real rendezvous, real packed-arena broadcast "
                          "(tiny weights), real plan_batches / barriers / max-over-ranks timing / rccl_ranks_seen, a stand-in for the GPU pipeline.  "
@@ -683,23 +720,32 @@ def main():
         else:
             lanes = GraphLanes([w.step for w in wls])
         graph = lanes.graphs[0]
-        if inflight > 1 and not args.no_single_stream:   # the same K steps one clip at a time: latency of a clip, reported beside the line
-            one = lanes
-            if args.config == 1:       # a ONE-lane capture of the serving object (a clip alone on the chip keeps the 3-deep GEMM ring: svcmi/serving.py)
-                cl1 = ClipLanes(model, whisper, wl.T, wl.B, lanes=1, device=device)
-                cl1.stage(0, mel=wl.mel, vec=wl.vec, pit=wl.pit, spk=wl.spk, lengths=wl.lengths)
-                one = cl1.capture().lanes
-            dt = timed(lambda: one.launch(0), one.synchronize, args.steps, args.warmup)
-            single = {"ms_per_step": round(1000.0 * dt / args.steps, 3),
-                      "value": round(wl.audio_seconds_per_step * world / (dt / args.steps), 2)}
-            if args.config == 1:
-                single["capture"] = "one-lane ClipLanes (3-deep GEMM ring)"
         run = lanes.launch
     else:
         run = wl.step
-    elapsed = timed(run, lanes.synchronize if lanes is not None else torch.cuda.synchronize, args.steps, args.warmup)
+    last = [None]       # what the newest step returned: a lane index (its output is lanes.outputs[i]) or the output tensor itself
+
+    def step():
+        last[0] = run()
+    torch.manual_seed(BENCH_SEED)       # the device draws of the warm-up and timed steps do not depend on what ran before them
+    elapsed = timed(step, lanes.synchronize if lanes is not None else torch.cuda.synchronize, args.steps, args.warmup)
     ms_per_step = 1000.0 * elapsed / args.steps
-    if os.environ.get("SVCMI_TIMELINE"):
+    if rank == 0 and args.dump_outputs:
+        out_t = lanes.outputs[last[0]] if isinstance(last[0], int) else last[0]
+        dump_outputs(args.dump_outputs, {"waveform": out_t})
+    if args.full and not args.eager and args.config != 3 and inflight > 1 and not args.no_single_stream:
+        # the same K steps one clip at a time: latency of a clip, reported beside the line
+        one = lanes
+        if args.config == 1:       # a ONE-lane capture of the serving object (a clip alone on the chip keeps the 3-deep GEMM ring: svcmi/serving.py)
+            cl1 = ClipLanes(model, whisper, wl.T, wl.B, lanes=1, device=device)
+            cl1.stage(0, mel=wl.mel, vec=wl.vec, pit=wl.pit, spk=wl.spk, lengths=wl.lengths)
+            one = cl1.capture().lanes
+        dt = timed(lambda: one.launch(0), one.synchronize, args.steps, args.warmup)
+        single = {"ms_per_step": round(1000.0 * dt / args.steps, 3),
+                  "value": round(wl.audio_seconds_per_step * world / (dt / args.steps), 2)}
+        if args.config == 1:
+            single["capture"] = "one-lane ClipLanes (3-deep GEMM ring)"
+    if args.full and os.environ.get("SVCMI_TIMELINE"):
         # In-flight timeline (probe library with -DSVCMI_PROBE_KTRACE=1 only; scripts/inflight_timeline.py): after the timed loop, record the
         # block stamps of N more steps in THIS launch regime and summarise them -- gemm_ms_per_step is measured, not inferred.
         import ctypes
@@ -731,7 +777,7 @@ def main():
         with open(os.environ["SVCMI_TIMELINE"], "w") as f:
             json.dump(summ, f, indent=1)
         log("timeline: " + json.dumps({k: v for k, v in summ.items() if k != "classes"}))
-    if os.environ.get("SVCMI_KTRACE_CLOCK"):       # timing-probe library (-DSVCMI_PROBE_KTRACE=1) only: the shader clock the GEMM K loops see in THIS launch regime
+    if args.full and os.environ.get("SVCMI_KTRACE_CLOCK"):       # timing-probe library (-DSVCMI_PROBE_KTRACE=1) only: the shader clock the GEMM K loops see in THIS launch regime
         import ctypes
         plib = ctypes.CDLL(os.environ["SVCMI_LIB"])
         cal = (ctypes.c_ulonglong * (16 * 8192 + 8))()
@@ -784,15 +830,15 @@ def main():
     }
     if single is not None:
         out["config"]["single_stream"] = single
-    perr = measured_precision_error(args.config, wprec, sprec)
-    if norm(wprec) or norm(sprec):
+    perr = measured_precision_error(args.config, wprec, sprec) if args.full else None
+    if args.full and (norm(wprec) or norm(sprec)):
         # measured HERE, on this run's inputs: the same step (same device RNG seed => same stochastic draws) in the line's mode and in
         # fp32 (the fp32 engine is pinned to the oracle at 2e-6: tests/test_gpu_engine.py), eager, outside the timed region
         live = live_precision_error(wl.one_batch if args.config == 3 else wl.step, whisper, model, norm(wprec), norm(sprec))
         perr = dict(perr or {"mode": norm(sprec) or norm(wprec)}, **live)
     if perr is not None:
         out["config"]["precision_error"] = perr
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         fn = wl.one_batch if args.config == 3 else wl.step
         agg = roofline_pass(wl, fn)
         total_ms = sum(a["ms"] for a in agg.values())
@@ -855,7 +901,7 @@ def main():
         sn = agg.get("svcmi_snake_alias_f32")
         if sn:
             out["snake_alias_GBs"] = round(sn["bytes"] / (sn["ms"] * 1e-3) / 1e9, 1)
-    if rank == 0 and world == 1 and args.config == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and args.config == 1 and not args.no_cpu_baseline:
         info, err = cpu_baseline(wl, wsd_cpu, vsd_cpu, hp)
         out["cpu_baseline"] = info
         out["parity_max_abs_vs_oracle"] = err

@@ -1,6 +1,7 @@
 """Generate tests/golden/*.npz by executing the REAL reference (build container only).
 
     python -m oracle.make_golden            # from the repo root; needs /root/reference
+    python -m oracle.make_golden pins       # only the fresh-seed, mean-filter, merge and export fixtures
 
 The reference holds no tests or golden vectors; these fixtures are the pin:
 outputs of the reference's own modules (``SynthesizerInfer``, ``Whisper.encoder``, ``svc_infer``) on
@@ -9,6 +10,7 @@ asserts that the oracle restatement agrees with the reference on every fixture b
 Weights are never stored: they are regenerated from their seed (oracle/weights.py); a checksum of
 the regenerated tensors is stored so RNG drift is detected instead of mis-reported as a parity bug.
 """
+import glob
 import os
 import sys
 import tempfile
@@ -25,6 +27,21 @@ from workload import weights as W
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 TOL = 5e-5
+
+
+def load(name, directory=OUT):
+    """tests/golden/<name>.npz merged with its <name>.<part>.npz companions (a fixture stored in parts keeps every file under 1 MiB)."""
+    g = dict(np.load(os.path.join(directory, name + ".npz")))
+    for part in sorted(glob.glob(os.path.join(directory, name + ".*.npz"))):
+        g.update(np.load(part))
+    return g
+
+
+def digest(t):
+    """sha256 of a tensor's dtype, shape and bytes: equal digests = the same tensor bit for bit."""
+    import hashlib
+    t = t.detach().contiguous().cpu()
+    return hashlib.sha256(f"{t.dtype}{tuple(t.shape)}".encode() + t.numpy().tobytes()).hexdigest()
 
 
 def checksum(tensors):
@@ -320,9 +337,79 @@ def config0_fixture(tag="config0_035"):
     _agree("svc_infer wave", torch.from_numpy(o_wav), torch.from_numpy(wav))
     assert wav.shape[0] == L - 1
     print(f"  T={T} frames, {wav.shape[0]} samples, rms {float(np.sqrt((wav ** 2).mean())):.3f}")
-    np.savez_compressed(os.path.join(OUT, tag + ".npz"), T=T, noise_seed=35, logmel=mel.numpy(), ppg=ppg, vec=vec, pit=pit.numpy(),
+    np.savez_compressed(os.path.join(OUT, tag + ".ppg.npz"), ppg=ppg)      # a part of its own: the fixture in one file is over 1 MiB (load())
+    np.savez_compressed(os.path.join(OUT, tag + ".npz"), T=T, noise_seed=35, logmel=mel.numpy(), vec=vec, pit=pit.numpy(),
                         wave=wav, whisper_checksum=checksum(ck["model_state_dict"]), hubert_checksum=checksum(hsd),
                         vits_checksum=checksum(sd), audio_checksum=checksum([torch.from_numpy(audio)]))
+
+
+def fresh_seed_fixture(tag="vits_tiny_T31_seed99"):
+    """The reference SynthesizerInfer on another seed and shape than vits_tiny_ragged (weights seed 99, one clip of T = 31)."""
+    print(f"[{tag}]")
+    hp = C.tiny_hp()
+    sd = W.make_vits_state(hp, seed=99)
+    ref = R.ref_synthesizer(hp, sd)
+    d = I.synth_clip(T=31, hp=hp, seed=5, B=1)
+    with torch.no_grad():
+        with R.injected_noise([d["src_noise"]], [d["rand_ini"]]):
+            src = ref.pitch2source(d["pit"])
+        with R.injected_noise([d["enc_noise"]]):
+            wav = ref.inference(d["ppg"], d["vec"], d["pit"], d["spk"], d["lengths"], src)
+        o = O.synth_inference(sd, hp, d["ppg"], d["vec"], d["pit"], d["spk"], d["lengths"],
+                              O.pitch2source(sd, hp, d["pit"], d["rand_ini"], d["src_noise"]), d["enc_noise"])
+    _agree("fresh-seed wave", o, wav)
+    np.savez_compressed(os.path.join(OUT, tag + ".npz"), wave=wav.numpy(), weights_checksum=checksum(sd))
+
+
+def mean_filter_fixture(tag="crepe_mean_filter"):
+    """The reference's crepe/filter.py:10-57 mean() on F0 tracks with NaNs, exact zeros and lengths below the window, repeated x2 as
+    pitch/inference.py:95 does: x_T<T>_w<win> (input) and mean_T<T>_w<win> (its output) for every case."""
+    import importlib.util
+    print(f"[{tag}]")
+    spec = importlib.util.spec_from_file_location("ref_crepe_filter", os.path.join(R.REF, "crepe", "filter.py"))
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)
+    g = torch.Generator().manual_seed(5)
+    out = {}
+    for T in (1, 2, 3, 4, 5, 6, 9, 64, 1001):
+        for win in (3, 5):
+            x = 50.0 + 900.0 * torch.rand(1, T, generator=g)
+            x[torch.rand(1, T, generator=g) < 0.2] = float("nan")
+            x[torch.rand(1, T, generator=g) < 0.1] = 0.0
+            x = torch.from_numpy(np.repeat(x.numpy(), 2, -1))
+            out[f"x_T{T}_w{win}"] = x.numpy()
+            out[f"mean_T{T}_w{win}"] = ref.mean(x.clone(), win).numpy()
+    np.savez_compressed(os.path.join(OUT, tag + ".npz"), **out)
+
+
+def merge_fixture(tag="svc_merge_tiny", every=16):
+    """The reference's svc_merge.merge_model(a, b, 0.7) and average_model([a, b, a]) on the tiny seeded states a (seed 3) and b (seed 4):
+    the key order of both results, the digest() of every value and the values of every ``every``-th key (the whole states would be
+    2.2 MB each)."""
+    import importlib.util
+    print(f"[{tag}]")
+    spec = importlib.util.spec_from_file_location("ref_svc_merge", os.path.join(R.REF, "svc_merge.py"))
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)
+    hp = C.tiny_hp()
+    a, b = W.make_vits_state(hp, seed=3), W.make_vits_state(hp, seed=4)
+    merged, averaged = ref.merge_model(a, b, 0.7), ref.average_model([a, b, a])
+    out = {"merge_keys": np.array(list(merged.keys())), "average_keys": np.array(list(averaged.keys())),
+           "merge_sha256": np.array([digest(v) for v in merged.values()]), "average_sha256": np.array([digest(v) for v in averaged.values()]),
+           "a_checksum": checksum(a), "b_checksum": checksum(b)}
+    for i, k in enumerate(list(merged.keys())[::every]):
+        out[f"merge_{i}"] = merged[k].numpy()
+        out[f"average_{i}"] = averaged[k].numpy()
+    np.savez_compressed(os.path.join(OUT, tag + ".npz"), every=every, **out)
+
+
+def export_keys_fixture(tag="svc_export_tiny_keys"):
+    """The state_dict key order of the reference SynthesizerInfer at the tiny config: svc_export.load_model (svc_export.py:10-27) walks
+    it and takes every key from the checkpoint, the module's own value where the checkpoint lacks one."""
+    print(f"[{tag}]")
+    hp = C.tiny_hp()
+    ref = R.ref_synthesizer(hp, W.make_vits_state(hp, seed=5))
+    np.savez_compressed(os.path.join(OUT, tag + ".npz"), keys=np.array(list(ref.state_dict().keys())))
 
 
 def main():
@@ -338,6 +425,10 @@ def main():
     hubert_fixture("hubert_soft_1s", n=16000, seed=3)
     crepe_fixture("crepe_full_1s", "full", n=16000, seed=5)
     config0_fixture()
+    fresh_seed_fixture()
+    mean_filter_fixture()
+    merge_fixture()
+    export_keys_fixture()
     print("golden fixtures written to", OUT)
 
 
@@ -345,5 +436,11 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "config0":
         assert R.available(), "needs /root/reference"
         config0_fixture()
+    elif len(sys.argv) > 1 and sys.argv[1] == "pins":
+        assert R.available(), "needs the reference sources (oracle/ref_import.py)"
+        fresh_seed_fixture()
+        mean_filter_fixture()
+        merge_fixture()
+        export_keys_fixture()
     else:
         main()

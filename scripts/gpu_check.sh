@@ -17,11 +17,11 @@ timeout 1500 python -m pytest tests -m gpu -q -s -p no:cacheprovider > $OUT/pyte
 grep -E "passed|failed|error" $OUT/pytest_gpu.log | tail -5
 fi
 echo "== bench"
-timeout 900 python bench.py --steps ${STEPS:-20} --warmup 3 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json; tail -5 $OUT/bench.err
+timeout 900 python bench.py --steps ${STEPS:-20} --warmup 3 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json; tail -5 $OUT/bench.err
 if [ "$SKIP_PROF" != "1" ]; then
 echo "== rocprofv3 kernel trace"
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o trace -- python $ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err; echo "rocprof rc=$?"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o trace -- python $ROOT/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err; echo "rocprof rc=$?"
 cd $ROOT
 find $OUT/prof -name "*stats*" | head; 
 F=$(find $OUT/prof -name "*kernel_stats.csv" | head -1); [ -n "$F" ] && head -25 "$F"

@@ -4,7 +4,7 @@
 rocprofv3 serialises the four HIP queues of the judged launch regime (4 clips in flight), so the regime the judged line is measured in had
 no kernel-level evidence.  A probe build of the library (scripts/build_variant.sh timeline -DSVCMI_PROBE_KTRACE=1; never the shipped one)
 makes EVERY block of every implicit-GEMM launch append {s_memrealtime at entry, at the end of its epilogue, output pointer, n_out << 32 | K,
-grid << 32 | rows} to a device ring (csrc/conv_gemm_body.h); `bench.py` with SVCMI_TIMELINE=<out.json> and SVCMI_LIB=<that build> runs its
+grid << 32 | rows} to a device ring (csrc/conv_gemm_body.h); `bench.py --full` with SVCMI_TIMELINE=<out.json> and SVCMI_LIB=<that build> runs its
 timed loop, then records a few more steps and hands the records to `summarise` below.
 
     launches      blocks with the same output pointer whose entries lie within `gap_us` of each other = one launch: [first entry, last exit]

@@ -6,6 +6,7 @@ Three builds (tests/emu/hip_emu.cpp):
                                                   (load it in a process started with LD_PRELOAD=<libasan.so>: tests/test_emu_hardened.py)
   build_emu(tls=True)       libsvcmi_emu_tls.so   -DSVCMI_EMU_TLS: per-block copies of `__shared__` -> SVCMI_EMU_BLOCKS=K interleaves K blocks
 """
+import fcntl
 import glob
 import os
 import subprocess
@@ -27,7 +28,16 @@ def asan_runtime():
 
 
 def build_emu(force=False, sanitize=False, tls=False, harness_only=False):
-    """harness_only: hip_emu.cpp alone (the scheduler + its self-test kernels, tests/test_emu_hardened.py) -- seconds instead of minutes."""
+    """harness_only: hip_emu.cpp alone (the scheduler + its self-test kernels, tests/test_emu_hardened.py) -- seconds instead of minutes.
+    Safe to call from concurrent processes (pytest -n N on a fresh checkout): one build at a time under a file lock, and the library
+    is renamed into place only once it is linked."""
+    os.makedirs(OUT_DIR, exist_ok=True)
+    with open(os.path.join(OUT_DIR, ".lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        return _build_emu(force, sanitize, tls, harness_only)
+
+
+def _build_emu(force, sanitize, tls, harness_only):
     kind = "san" if sanitize else ("tls" if tls else "")
     extra = os.environ.get("SVCMI_EMU_CXXFLAGS", "").split()      # build experiments (-DSVCMI_...=...): the same switches as scripts/build_variant.sh
     if extra:
@@ -57,10 +67,11 @@ def build_emu(force=False, sanitize=False, tls=False, harness_only=False):
     if any([p.wait() for p in procs]):
         raise RuntimeError("emulator build failed")
     objs = [j[-1] for j in jobs]
-    link = ["g++", "-shared", "-pthread", "-o", out] + objs
+    link = ["g++", "-shared", "-pthread", "-o", out + ".tmp"] + objs
     if sanitize:
         link[1:1] = ["-fsanitize=address,undefined"]
     subprocess.run(link, check=True)
+    os.replace(out + ".tmp", out)
     return out
 
 

@@ -9,6 +9,7 @@ import torch
 from workload import config as C
 from workload import inputs as I
 from oracle import svc_oracle as O
+from oracle.make_golden import load as load_golden
 from workload import weights as W
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -17,7 +18,7 @@ TIGHT = 1e-4        # what fp32 kernels are expected to reach (reported, asserte
 
 
 def golden(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"))
+    return load_golden(name, GOLDEN)
 
 
 def _t(a):

@@ -10,13 +10,13 @@ from workload import config as C
 from workload import inputs as I
 from oracle import svc_oracle as O
 from workload import weights as W
-from oracle.make_golden import checksum
+from oracle.make_golden import checksum, load
 
 TOL = 5e-5   # fp32 CPU vs fp32 CPU (different BLAS blocking across hosts); waveform in [-1,1]
 
 
 def _load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name + ".npz"))
+    return load(name, golden_dir)
 
 
 def _t(a):
@@ -96,22 +96,19 @@ def test_svc_infer_two_chunks_against_reference_golden(golden_dir):
     assert np.abs(wav[-2000:] - g["wave_tail"]).max() <= TOL
 
 
-@pytest.mark.needs_reference
-def test_oracle_equals_live_reference_on_fresh_seed():
-    """Not just the stored vectors: a different seed/shape through the imported reference."""
-    from oracle import ref_import as R
+def test_oracle_equals_live_reference_on_fresh_seed(golden_dir):
+    """Not just the fixtures above: another seed and shape (weights seed 99, T = 31), as the reference computed it
+    (make_golden.fresh_seed_fixture)."""
+    g = _load(golden_dir, "vits_tiny_T31_seed99")
     hp = C.tiny_hp()
     sd = W.make_vits_state(hp, seed=99)
-    ref = R.ref_synthesizer(hp, sd)
+    assert abs(checksum(sd) - float(g["weights_checksum"])) <= 1e-6 * abs(float(g["weights_checksum"]))
     d = I.synth_clip(T=31, hp=hp, seed=5, B=1)
     with torch.no_grad():
-        with R.injected_noise([d["src_noise"]], [d["rand_ini"]]):
-            src = ref.pitch2source(d["pit"])
-        with R.injected_noise([d["enc_noise"]]):
-            wav = ref.inference(d["ppg"], d["vec"], d["pit"], d["spk"], d["lengths"], src)
         o = O.synth_inference(sd, hp, d["ppg"], d["vec"], d["pit"], d["spk"], d["lengths"],
                               O.pitch2source(sd, hp, d["pit"], d["rand_ini"], d["src_noise"]), d["enc_noise"])
-    assert (o - wav).abs().max() <= TOL
+    wav = _t(g["wave"])
+    assert o.shape == wav.shape and (o - wav).abs().max() <= TOL
 
 
 def test_logmel_oracle_matches_reference_golden(golden_dir):
@@ -173,26 +170,19 @@ def test_viterbi_restatement_on_a_known_case():
     assert CO.viterbi_path(prob, np.full((3, 3), 1 / 3)).tolist() == [0, 1, 0]
 
 
-@pytest.mark.needs_reference
-def test_crepe_mean_filter_oracle_matches_the_reference_filter():
+def test_crepe_mean_filter_oracle_matches_the_reference_filter(golden_dir):
     """the tail of compute_f0_sing (np.repeat x2 + crepe.filter.mean(5), pitch/inference.py:95-97) was only
-    compared oracle-to-engine.  Here the oracle's mean_filter and the engine's numpy form run against the reference's own
-    crepe/filter.py:10-57 (imported from /root/reference) on tracks with NaNs, exact zeros and lengths below the window."""
-    import importlib.util
+    compared oracle-to-engine.  Here the oracle's mean_filter and the engine's numpy form run against what the reference's own
+    crepe/filter.py:10-57 returned (make_golden.mean_filter_fixture) on tracks with NaNs, exact zeros and lengths below the window."""
     import numpy as np
     from oracle import crepe_oracle as CO
     from svcmi.pitch import inference as PI
-    spec = importlib.util.spec_from_file_location("ref_crepe_filter", "/root/reference/crepe/filter.py")
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    g = torch.Generator().manual_seed(5)
+    fx = _load(golden_dir, "crepe_mean_filter")
     for T in (1, 2, 3, 4, 5, 6, 9, 64, 1001):
         for win in (3, 5):
-            x = 50.0 + 900.0 * torch.rand(1, T, generator=g)
-            x[torch.rand(1, T, generator=g) < 0.2] = float("nan")
-            x[torch.rand(1, T, generator=g) < 0.1] = 0.0
-            x = torch.from_numpy(np.repeat(x.numpy(), 2, -1))              # pitch/inference.py:95
-            want = ref.mean(x.clone(), win)
+            x = _t(fx[f"x_T{T}_w{win}"])                                  # repeated x2 as pitch/inference.py:95 does
+            want = _t(fx[f"mean_T{T}_w{win}"])
+            assert x.shape == (1, 2 * T) and want.shape == x.shape
             assert torch.allclose(CO.mean_filter(x.clone(), win), want, rtol=0, atol=0, equal_nan=True)
             got = PI._mean_filter_np(x[0].numpy(), win)
             assert got.shape == (2 * T,) and np.allclose(got, want[0].numpy(), rtol=1e-6, atol=0, equal_nan=True)
