@@ -260,7 +260,7 @@ def pitch2source(sd, hp, f0, rand_ini, noise):
     sr = float(hp.data.sampling_rate)
     up = f0.repeat_interleave(hop, dim=1)                            # nearest upsample (generator.py:63-64)
     B, L = up.shape
-    harm = torch.arange(1, C.NSF_HARMONICS + 1, dtype=torch.float32)
+    harm = torch.arange(1, C.NSF_HARMONICS + 1, dtype=f0.dtype)
     f0_buf = up.unsqueeze(-1) * harm                                  # nsf.py:293-297
     rad = (f0_buf / sr) % 1
     ini = rand_ini.clone()
@@ -270,7 +270,7 @@ def pitch2source(sd, hp, f0, rand_ini, noise):
     shift = torch.zeros_like(rad)
     shift[:, 1:, :] = ((over[:, 1:, :] - over[:, :-1, :]) < 0) * -1.0
     sines = torch.sin(torch.cumsum(rad + shift, dim=1) * 2 * np.pi) * C.NSF_SINE_AMP
-    uv = (up > 0).float().unsqueeze(-1)
+    uv = (up > 0).to(up.dtype).unsqueeze(-1)
     noise_amp = uv * C.NSF_NOISE_STD + (1 - uv) * C.NSF_SINE_AMP / 3
     sines = sines * uv + noise_amp * noise
     merged = torch.tanh(F.linear(sines, sd["dec.m_source.merge_w"]) + sd["dec.m_source.merge_b"])
@@ -314,7 +314,8 @@ def audio_encoder(wsd, mel, n_head, n_layer):
         q = q.view(Bq, Tw, n_head, dh).permute(0, 2, 1, 3) * scale       # model.py:88-101
         k = k.view(Bq, Tw, n_head, dh).permute(0, 2, 3, 1) * scale
         v = v.view(Bq, Tw, n_head, dh).permute(0, 2, 1, 3)
-        w = F.softmax((q @ k).float(), dim=-1)
+        qk = q @ k
+        w = F.softmax(qk if qk.dtype == torch.float64 else qk.float(), dim=-1)     # (an fp64 evaluation stays fp64)
         a = (w @ v).permute(0, 2, 1, 3).flatten(start_dim=2)
         x = x + F.linear(a, wsd[b + ".attn.out.weight"], wsd[b + ".attn.out.bias"])
         h = F.layer_norm(x, (S,), wsd[b + ".mlp_ln.weight"], wsd[b + ".mlp_ln.bias"])

@@ -418,28 +418,44 @@ def check_whisper_stress(ops, device, dims, n, tol=TIGHT):
     return dict(err=err, out_max=scale)
 
 
-def check_whisper_batched_rows_flattened(ops, device, dims, B=3, n=90, small_m_rows=48, tol=TIGHT):
-    """Batched windows above ``small_m_rows`` GEMM rows: the four k = 1 projections of a block see ONE matrix of B * tw rows (M tiles span
-    batch items, host_stages.hip: whisper_fwd).  Every item equals its solo run on the library's own tiles (bit for bit) and the oracle."""
+def check_whisper_batched_rows_flattened(ops, device, dims, B=3, n=90, small_m_rows=48, tol=TIGHT, oracle_items=None, solo_bits=True):
+    """Batched windows above ``small_m_rows`` GEMM rows (None: the library's default threshold): the four k = 1 projections of a block see
+    ONE matrix of B * tw rows (M tiles span batch items, host_stages.hip: whisper_fwd).  Every item equals the same batch run unflattened
+    on the library's tiles without K slices, and its solo run on the library's own tiles -- bit for bit; with ``solo_bits`` False to
+    TIGHT only: at production size the conv stem's dispatch depends on the batch size (B = 1 at n = 1000: 64x64 tiles with 8 K slices
+    in conv2; B = 16: 128x64 tiles, none), which the flattening does not touch.  ``oracle_items`` (default: all) also match the oracle
+    and pass check_whisper_fp64 in the flattened batch."""
     from svcmi.whisper.inference import load_model
     ck = W.make_whisper_state(dims)
     wm = load_model(ck, device, ops=ops)
-    wm.encoder.small_m_rows = small_m_rows
+    enc = wm.encoder
+    enc.small_m_rows = small_m_rows or 0
     g = torch.Generator().manual_seed(n + B)
     mel = (torch.randn(B, 80, n, generator=g) * 0.5).clamp(-1, 1.5)
     nz = torch.randn(B, 80, n, generator=g)
     tw = (n - 1) // 2 + 1
-    assert B * tw > small_m_rows >= tw, "batched rows above the threshold, one item below it"
-    out = wm.encoder(mel, nz, 0.1)
-    wm.encoder.small_m_rows = 1                 # solo runs on the same (library-chosen) tiles: a lone item is never flattened (B = 1)
+    assert B * tw > (small_m_rows or 1024) >= tw, "batched rows above the threshold, one item below it"
+    out = enc(mel, nz, 0.1)
+    # the same batch, not flattened: per-item projections on the library's tiles (-1), no K slices (-1), the batch's own stem launches
+    enc.small_m_rows, enc.split_o, enc.split_mlp = 1 << 30, -1, -1
+    enc.tile_qkv = enc.tile_o = enc.tile_mlp1 = enc.tile_mlp2 = -1
+    unflat = enc(mel, nz, 0.1)
+    enc.split_o = enc.split_mlp = enc.tile_qkv = enc.tile_o = enc.tile_mlp1 = enc.tile_mlp2 = 0
     for i in range(B):
-        solo = wm.encoder(mel[i:i + 1], nz[i:i + 1], 0.1)
-        assert torch.equal(out[i:i + 1], solo), f"item {i}: max diff {float((out[i:i + 1] - solo).abs().max()):.3e}"
+        assert torch.equal(out[i:i + 1], unflat[i:i + 1]), f"item {i} vs unflattened: max diff {float((out[i:i + 1] - unflat[i:i + 1]).abs().max()):.3e}"
+    enc.small_m_rows = 1                 # solo runs on the same (library-chosen) tiles: a lone item is never flattened (B = 1)
+    for i in range(B):
+        solo = enc(mel[i:i + 1], nz[i:i + 1], 0.1)
+        diff = float((out[i:i + 1] - solo).abs().max())
+        assert diff == 0.0 if solo_bits else diff <= tol * max(1.0, float(solo.abs().max())), f"item {i} vs solo: max diff {diff:.3e}"
+    enc.small_m_rows = small_m_rows or 0
+    items = list(range(B)) if oracle_items is None else list(oracle_items)
     with torch.no_grad():
-        ref = O.audio_encoder(ck["model_state_dict"], mel + 0.1 * nz, dims["n_audio_head"], O.whisper_kept_layers(dims))
-    err = maxerr(out, ref)
+        ref = O.audio_encoder(ck["model_state_dict"], (mel + 0.1 * nz)[items], dims["n_audio_head"], O.whisper_kept_layers(dims))
+    err = maxerr(out[items], ref)
     assert err <= tol * max(1.0, float(ref.abs().max())), err
-    return err
+    rows = check_whisper_fp64(wm, ck, dims, mel + 0.1 * nz, items, title=f"whisper B = {B} x n = {n}, flattened")
+    return err, rows
 
 
 def stress_floor(sd, hp, d, lens, o_src, o_wav, wav):
@@ -454,6 +470,158 @@ def stress_floor(sd, hp, d, lens, o_src, o_wav, wav):
     floor = float((o_wav.double() - o64).abs().max())
     assert floor <= 3e-4, f"stress set is ill-conditioned: fp32 vs fp64 oracle {floor:.2e}"
     return dict(oracle_fp32_vs_fp64=floor, wave_vs_fp64=float((wav.detach().cpu().double() - o64).abs().max()))
+
+
+# ----------------------------------------------------------------------------- stage-by-stage parity against the fp64 oracle
+# Each stage of the engine starts from the fp64 result of the stage before it, rounded to fp32, and is compared with the oracle stage
+# evaluated in fp64 on those same fp32 inputs (ref64).  The oracle's own fp32 run on the CPU (ref32) measures what "fp32 class" means
+# for that stage: e = |. - ref64|max / max(1, |ref64|max); e_eng must stay within STAGE_FACTOR * e_cpu, at least STAGE_FLOOR and never
+# above STAGE_CAP -- about 20x tighter than the waveform bar WAVE_TOL at the shapes the benchmark runs.
+STAGE_FACTOR, STAGE_FLOOR, STAGE_CAP = 8.0, 2e-6, 5e-5
+SYNTH_STAGES = ("pitch2source", "z_p", "z", "wave")
+
+
+def _f64(sd):
+    return {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+
+
+def stage_row(name, eng, ref64, ref32):
+    """(name, e_eng, e_cpu, bar) of one stage."""
+    scale = max(1.0, float(ref64.abs().max()))
+    e_eng = float((eng.detach().cpu().double() - ref64).abs().max()) / scale
+    e_cpu = float((ref32.detach().cpu().double() - ref64).abs().max()) / scale
+    return name, e_eng, e_cpu, min(max(STAGE_FACTOR * e_cpu, STAGE_FLOOR), STAGE_CAP)
+
+
+class StageParityError(AssertionError):
+    """An engine stage above its fp64 bar; ``rows`` = {stage: {e_eng, e_cpu, bar}}."""
+
+    def __init__(self, msg, rows):
+        super().__init__(msg)
+        self.rows = rows
+
+
+def stage_report(rows, title):
+    """Print one row per stage, then fail if any stage's engine error is above its bar (a NaN fails too)."""
+    lines = [f"{title}:  {'stage':<22s} {'e_eng':>9s} {'e_cpu':>9s} {'bar':>9s}"]
+    lines += [f"  {n:<22s} {a:9.2e} {b:9.2e} {c:9.2e}{'' if a <= c else '   <-- above the bar'}" for n, a, b, c in rows]
+    print("\n".join(lines))
+    table = {n: dict(e_eng=a, e_cpu=b, bar=c) for n, a, b, c in rows}
+    if not all(a <= c for _, a, _, c in rows):
+        raise StageParityError("engine stage error above its fp64 bar\n" + "\n".join(lines), table)
+    return table
+
+
+def synth_stage_refs(sd, hp, d, items=None, stages=SYNTH_STAGES):
+    """The oracle side of check_stages_fp64 for the batch items ``items`` of the inputs ``d`` (a workload.inputs.synth_clip dict): per
+    stage its fp32 input x32 (the fp64 upstream result, rounded), ref64 and ref32 ([n, C, T] / [n, L] for pitch2source).  Items are
+    independent, so the oracle runs on the sub-batch only."""
+    B, T = d["pit"].shape
+    items = list(range(B)) if items is None else list(items)
+    x = {k: v[items] for k, v in d.items()}
+    sd64, x64 = _f64(sd), {k: (v.double() if v.is_floating_point() else v) for k, v in x.items()}
+    refs = {"items": items, "stages": tuple(stages)}
+    with torch.no_grad():
+        src64 = O.pitch2source(sd64, hp, x64["pit"], x64["rand_ini"], x64["src_noise"]).flatten(1)
+        if "pitch2source" in stages:
+            refs["pitch2source"] = (None, src64, O.pitch2source(sd, hp, x["pit"], x["rand_ini"], x["src_noise"]).flatten(1))
+        # coarse pitch bins once, in fp32 as the engine computes them (csrc/vits_elem.hip: f0_to_coarse_dev): one flipped bin would
+        # otherwise dominate the comparison
+        f0c = O.f0_to_coarse(x["pit"].float())
+        zp64 = O.text_encoder(sd64, x64["ppg"], x64["vec"], f0c, x["lengths"], x64["enc_noise"])[0]
+        if "z_p" in stages:
+            refs["z_p"] = (None, zp64, O.text_encoder(sd, x["ppg"], x["vec"], f0c, x["lengths"], x["enc_noise"])[0])
+        mask = O.sequence_mask(x["lengths"], T)
+        xf = zp64.float()
+        z64 = O.flow_reverse(sd64, xf.double(), mask.double(), x64["spk"]) * mask
+        if "z" in stages:
+            refs["z"] = (xf, z64, O.flow_reverse(sd, xf, mask, x["spk"]) * mask)
+        if "wave" in stages:
+            xg, sg = z64.float(), src64.float()
+            refs["wave"] = ((xg, sg), O.generator_inference(sd64, hp, x64["spk"], xg.double(), sg.double().unsqueeze(1)).flatten(1),
+                            O.generator_inference(sd, hp, x["spk"], xg, sg.unsqueeze(1)).flatten(1))
+    return refs
+
+
+def check_stages_fp64(m, sd, hp, d, items=None, stages=SYNTH_STAGES, refs=None, title="synthesizer stages"):
+    """pitch2source, text encoder -> z_p, reverse flow -> z, generator -> wave of the engine ``m`` (a SynthesizerInfer) against the fp64
+    oracle, stage by stage (see STAGE_FACTOR).  The engine runs the WHOLE batch of ``d`` (its batch-size-dependent dispatch is what is
+    tested): the per-stage entry points with the flow / generator inputs of the checked ``items`` replaced by the rounded fp64 upstream
+    results (the other items keep the engine's own).  ``refs``: synth_stage_refs(...) computed earlier for the same inputs."""
+    refs = refs or synth_stage_refs(sd, hp, d, items, stages)
+    items, stages = refs["items"], refs["stages"]
+    ops, w = m.ops, m._weights()
+    dev = m._device
+    B, T = d["pit"].shape
+    on = lambda t: t.to(dev, torch.float32).contiguous()
+    pit, spk, lens = on(d["pit"]), on(d["spk"]), d["lengths"].to(dev, torch.int32).contiguous()
+    src = m.pitch2source(pit, noise=(d["rand_ini"], d["src_noise"])).view(B, -1)
+    args = (m._cmodel(), on(d["ppg"]), on(d["vec"]), pit, spk, lens)
+    if len(items) < B:
+        _, z_p, z = ops.synth_stages_fwd(*args, src, on(d["enc_noise"]))
+    else:                                   # every item's stage inputs come from the references
+        z_p = z = torch.empty(B, T, w.I, device=dev)
+    flow_in = gen_in = None
+    src_in = src.clone()
+    idx = torch.tensor(items, device=dev)
+    if "z" in stages:
+        flow_in = z_p.clone()
+        flow_in[idx] = on(refs["z"][0].transpose(1, 2))
+    if "wave" in stages:
+        gen_in = z.clone()
+        gen_in[idx] = on(refs["wave"][0][0].transpose(1, 2))
+        src_in[idx] = on(refs["wave"][0][1])
+    wave, z_p, z = ops.synth_stages_fwd(*args, src_in, on(d["enc_noise"]), flow_in=flow_in, gen_in=gen_in)
+    mask = O.sequence_mask(d["lengths"][items], T)
+    eng = {"pitch2source": src[idx], "z_p": z_p[idx].transpose(1, 2), "z": z[idx].transpose(1, 2).cpu() * mask, "wave": wave[idx].flatten(1)}
+    rows = [stage_row(k, eng[k], refs[k][1], refs[k][2]) for k in SYNTH_STAGES if k in stages]
+    return stage_report(rows, f"{title} (B = {B} x T = {T}, items {items})")
+
+
+def check_whisper_fp64(wm, ck, dims, mel, items=None, title="whisper"):
+    """The Whisper encoder of ``wm`` against the fp64 oracle (see STAGE_FACTOR) on the fp32 mel ``mel`` [B, 80, n] -- already holding
+    mel + 0.1 * noise, and passed without a noise argument, so that engine and oracle read the same bits.  The engine runs the whole
+    batch; the oracle the chosen ``items`` (one row each)."""
+    B = mel.shape[0]
+    items = list(range(B)) if items is None else list(items)
+    out = wm.encoder(mel, None).cpu()
+    wsd, heads, layers = ck["model_state_dict"], dims["n_audio_head"], O.whisper_kept_layers(dims)
+    wsd64 = _f64(wsd)
+    rows = []
+    with torch.no_grad():
+        for i in items:
+            ref64 = O.audio_encoder(wsd64, mel[i:i + 1].double(), heads, layers)
+            ref32 = O.audio_encoder(wsd, mel[i:i + 1], heads, layers)
+            rows.append(stage_row(f"ppg item {i}", out[i:i + 1], ref64, ref32))
+    return stage_report(rows, f"{title} (B = {B} x n = {mel.shape[-1]})")
+
+
+def check_perturbation_caught(ops, device, hp, d, delta, refs=None, o_wav=None, key="dec.conv_post.weight"):
+    """The stage bars catch what the waveform bar misses: ``key`` scaled by 1 + ``delta`` in the ENGINE's copy of the weights only.  The
+    waveform still passes the north-star criterion (<= WAVE_TOL against the fp32 oracle on the same inputs and noise), while
+    check_stages_fp64 fails.  ``refs`` / ``o_wav``: the unperturbed oracle results for ``d``, if already computed.
+    Returns (waveform error, the stage table of the failed check)."""
+    from svcmi import SynthesizerInfer
+    sd = W.make_vits_state(hp, seed=1234)
+    m = SynthesizerInfer(hp.data.filter_length // 2 + 1, hp.data.segment_size // hp.data.hop_length, hp, ops=ops)
+    m.load_state_dict(dict(sd, **{key: sd[key] * (1.0 + delta)}))
+    m.eval()
+    m.to(device)
+    src = m.pitch2source(d["pit"], noise=(d["rand_ini"], d["src_noise"]))
+    wav = m.inference(d["ppg"], d["vec"], d["pit"], d["spk"], d["lengths"], src, noise=d["enc_noise"])
+    if o_wav is None:
+        with torch.no_grad():
+            o_src = O.pitch2source(sd, hp, d["pit"], d["rand_ini"], d["src_noise"])
+            o_wav = O.synth_inference(sd, hp, d["ppg"], d["vec"], d["pit"], d["spk"], d["lengths"], o_src, d["enc_noise"])
+    e_wav = maxerr(wav, o_wav)
+    assert e_wav <= WAVE_TOL, e_wav
+    with pytest.raises(StageParityError) as caught:
+        check_stages_fp64(m, sd, hp, d, refs=refs, title=f"{key} x (1 + {delta:g}) in the engine only")
+    rows = caught.value.rows
+    assert rows["wave"]["e_eng"] > rows["wave"]["bar"], rows
+    print(f"perturbation {key} x (1 + {delta:g}): waveform err {e_wav:.2e} <= {WAVE_TOL:g}; wave stage e_eng {rows['wave']['e_eng']:.2e} "
+          f"> bar {rows['wave']['bar']:.2e}")
+    return e_wav, rows
 
 
 def check_streaming_decoder(ops, device, hp, T, tiles, B=1, seed=41, precision=None):

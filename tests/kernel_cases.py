@@ -102,6 +102,15 @@ CONV_CASES_LP_SMALL = [
     dict(id="lp_f16_splitk_auto_out16", B=1, T=33, cin=16, n=8, k=63, pad=31, split_k=0, prec="f16", out16=True),
     dict(id="a16_bf16_splitk_auto_out16", B=1, T=40, cin=64, n=16, k=21, pad=10, split_k=0, prec="bf16", a16=True, out16=True),
 ]
+# configs[3]: the four k = 1 projections of a Whisper block over 16 windows x 500 rows flattened into ONE M = 8000 matrix (host_stages.hip:
+# whisper_fwd), automatic tiles (fp32: 128x128 for QKV / MLP-up, 128x64 for the N = 1280 projections; the last 128-row tile is ragged), no
+# K slices
+WHISPER_FLAT = [
+    dict(id="whisper_flat_qkv", B=1, T=8000, cin=1280, n=3840, k=1),
+    dict(id="whisper_flat_out_res", B=1, T=8000, cin=1280, n=1280, k=1, res=True),
+    dict(id="whisper_flat_mlp1_gelu", B=1, T=8000, cin=1280, n=5120, k=1, act=ACT_GELU),
+    dict(id="whisper_flat_mlp2_res", B=1, T=8000, cin=5120, n=1280, k=1, res=True),
+]
 CONV_CASES_LP_LARGE = [
     dict(id="lp_whisper_qkv_bf16x3", B=1, T=750, cin=1280, n=3840, k=1, prec="bf16x3"),
     dict(id="lp_whisper_mlp2_res_f16", B=1, T=500, cin=5120, n=1280, k=1, res=True, prec="f16", split_k=4),
@@ -115,7 +124,8 @@ CONV_CASES_LP_LARGE = [
     dict(id="a16_whisper_qkv_x3", B=1, T=750, cin=1280, n=3840, k=1, prec="bf16x3", a16=True),
     dict(id="a16_whisper_mlp1_gelu_out16_x3", B=2, T=500, cin=1280, n=5120, k=1, prec="bf16x3", a16=True, out16=True, act=ACT_GELU),
     dict(id="a16_whisper_mlp2_x3_splitk4", B=1, T=500, cin=5120, n=1280, k=1, res=True, prec="bf16x3", a16=True, split_k=4),
-]
+] + [dict(c, id=f"a16_f16_{c['id']}", prec="f16", a16=True, out16=c["id"].endswith("mlp1_gelu")) for c in WHISPER_FLAT] \
+  + [dict(c, id=f"lp_bf16x3_{c['id']}", prec="bf16x3") for c in WHISPER_FLAT]
 CONV_CASES_LARGE = [
     dict(id="whisper_qkv", B=1, T=500, cin=1280, n=3840, k=1),
     dict(id="whisper_mlp2_res", B=1, T=500, cin=5120, n=1280, k=1, res=True),
@@ -123,7 +133,7 @@ CONV_CASES_LARGE = [
     dict(id="amp_k11_d5", B=1, T=5000, cin=160, n=160, k=11, dil=5, pad=25, res=True),
     dict(id="stage4_c12_k11", B=1, T=40000, cin=12, n=12, k=11, pad=5, res=True),
     dict(id="auto_tile_big", B=2, T=20000, cin=80, n=80, k=7, pad=3),
-]
+] + WHISPER_FLAT
 
 
 def check_conv(ops, c, device):
@@ -225,22 +235,24 @@ def check_conv_ring2(ops, device, tile, n, cin=64, k=5, T=150, B=2):
     _close(y2, ref, 2e-5, f"ring2 tile {tile}")
     return True
 
-def check_conv_w8(ops, device, n, cin=64, k=3, T=300, B=2, partials=False):
-    """SVCMI_CONV_TILE_P16W8_128x80 (tile 10: the 64x80 wave tile on eight-wave blocks) against SVCMI_CONV_TILE_P16_64x80 (tile 6): the same
-    wave tile and the same K order, so the same bits -- full launches (bias, GELU, residual) and raw split-K slabs, both ring depths."""
+def check_conv_w8(ops, device, n, cin=64, k=3, T=300, B=2, partials=False, tiles=(6, 10)):
+    """Tiles that walk K with the same MFMA sequence give the same bits -- full launches (bias, GELU, residual) and raw split-K slabs, both
+    ring depths.  Default pair: SVCMI_CONV_TILE_P16W8_128x80 (tile 10: the 64x80 wave tile on eight-wave blocks) against
+    SVCMI_CONV_TILE_P16_64x80 (tile 6).  ``tiles``: every tile is compared with the first one."""
     g = _g(1000 + n + cin + k)
     x = (torch.randn(B, T, cin, generator=g)).to(device)
     w = PW.pack_conv(torch.randn(n, cin, k, generator=g) / math.sqrt(cin * k)).to(device)
     bias = torch.randn(n, generator=g).to(device)
     res = torch.randn(B, T, n, generator=g).to(device)
     for ring in (0, 16):
-        if partials:
-            y6 = ops.conv(x, w, None, ksize=k, pad=(k - 1) // 2, tile=6 | ring, split_k=2, partials=True)
-            y10 = ops.conv(x, w, None, ksize=k, pad=(k - 1) // 2, tile=10 | ring, split_k=2, partials=True)
-        else:
-            y6 = ops.conv(x, w, bias, ksize=k, pad=(k - 1) // 2, act=ACT_GELU, res=res, split_k=1, tile=6 | ring)
-            y10 = ops.conv(x, w, bias, ksize=k, pad=(k - 1) // 2, act=ACT_GELU, res=res, split_k=1, tile=10 | ring)
-        assert torch.equal(y6, y10), (n, cin, k, ring, float((y6 - y10).abs().max()))
+        ys = []
+        for tile in tiles:
+            if partials:
+                ys.append(ops.conv(x, w, None, ksize=k, pad=(k - 1) // 2, tile=tile | ring, split_k=2, partials=True).clone())
+            else:
+                ys.append(ops.conv(x, w, bias, ksize=k, pad=(k - 1) // 2, act=ACT_GELU, res=res, split_k=1, tile=tile | ring))
+        for tile, y in zip(tiles[1:], ys[1:]):
+            assert torch.equal(ys[0], y), (n, cin, k, ring, tiles[0], tile, float((ys[0] - y).abs().max()))
     return True
 
 
@@ -417,8 +429,10 @@ def check_channel_norm_gelu(ops, device, B=2, T=700, c=32):
     _close(got, want, 2e-5, "channel_norm_gelu")
 
 
-def check_splitk_layernorm(ops, device, B=2, S=3, T=7, c=1280):
-    """conv(partials=True) slabs -> fused reduce + bias + residual + LayerNorm, vs the unsplit conv + torch layer_norm."""
+def check_splitk_layernorm(ops, device, B=2, S=3, T=7, c=1280, flat=False):
+    """conv(partials=True) slabs -> fused reduce + bias + residual + LayerNorm, vs the unsplit conv + torch layer_norm.
+    ``flat``: the flattened Whisper path (host_stages.hip: whisper_fwd, B * tw > small_m_rows) -- ONE launch over M = B * T rows writes
+    the slabs [1][S][B*T][c], which splitk_layernorm reads as [B][S][T][c]; the two layouts agree only for S = 1, which flattening forces."""
     g = _g(100 + c + S)
     cin = 64 * S
     a = torch.randn(B, T, cin, generator=g)
@@ -429,7 +443,13 @@ def check_splitk_layernorm(ops, device, B=2, S=3, T=7, c=1280):
     y_ref = F.layer_norm(x_ref, (c,), gamma, beta, 1e-5)
     dev = lambda t: t.to(device)
     xd = dev(x.clone())
-    part = ops.conv(dev(a), PW.pack_conv(w).to(device), None, partials=True, split_k=S)
+    if flat:
+        assert S == 1, "the flattened path runs its projections without K slices"
+        part = ops.conv(dev(a).reshape(1, B * T, cin), PW.pack_conv(w).to(device), None, partials=True, split_k=S)
+        assert tuple(part.shape) == (1, S, B * T, c)
+        part = part.view(B, S, T, c)
+    else:
+        part = ops.conv(dev(a), PW.pack_conv(w).to(device), None, partials=True, split_k=S)
     assert tuple(part.shape) == (B, S, T, c)
     y = ops.splitk_layernorm(part, dev(bias), xd, dev(gamma), dev(beta))
     _close(xd, x_ref, 2e-5, "splitk_ln residual stream")

@@ -2,10 +2,15 @@
 executed on the CPU SIMT emulator at the tiny configuration and compared with the golden vectors of
 the real reference.  Slow-ish (fibers), sized to stay within the CPU test budget."""
 import pytest
+import torch
 
 from workload import config as C
+from workload import inputs as I
+from workload import weights as W
 from tests import engine_cases as E
 from tests.emu import emu_ops
+
+PERTURBATION = 1e-3          # relative change of one engine weight tensor: invisible to WAVE_TOL, caught by the stage bars
 
 
 @pytest.fixture(scope="module")
@@ -89,3 +94,30 @@ def test_outlier_stress_weights_whisper_and_generator(ops):
     """parity must not rest on N(0, sigma) weights only."""
     print(E.check_whisper_stress(ops, "cpu", C.WHISPER_TINY_TEST, n=120))
     print(E.check_generator_widths_against_oracle(ops, "cpu", T=3, B=1, stress=True))
+
+
+def _stage_clip(hp):
+    d = I.synth_clip(T=7, hp=hp, seed=5, B=2)
+    d["lengths"][1] = 5                      # ragged: the masks of every stage
+    return d
+
+
+def test_stages_against_the_fp64_oracle(ops):
+    """Every synthesizer stage from the rounded fp64 result of the stage before it, against the oracle in fp64 (E.check_stages_fp64)."""
+    hp = C.tiny_hp()
+    m, sd = E.make_model(hp, ops, "cpu")
+    E.check_stages_fp64(m, sd, hp, _stage_clip(hp))
+
+
+def test_whisper_against_the_fp64_oracle(ops):
+    from svcmi.whisper.inference import load_model
+    ck = W.make_whisper_state(C.WHISPER_TINY_TEST)
+    wm = load_model(ck, "cpu", ops=ops)
+    g = torch.Generator().manual_seed(12)
+    mel = (torch.randn(2, 80, 60, generator=g) * 0.5).clamp(-1, 1.5) + 0.1 * torch.randn(2, 80, 60, generator=g)
+    E.check_whisper_fp64(wm, ck, C.WHISPER_TINY_TEST, mel)
+
+
+def test_stage_bars_catch_a_perturbation_the_waveform_bar_misses(ops):
+    hp = C.tiny_hp()
+    print(E.check_perturbation_caught(ops, "cpu", hp, _stage_clip(hp), PERTURBATION))

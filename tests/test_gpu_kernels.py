@@ -68,6 +68,11 @@ def test_splitk_layernorm(ops, S, c):
     K.check_splitk_layernorm(ops, "cuda", S=S, c=c)
 
 
+def test_splitk_layernorm_reads_the_flattened_whisper_slabs(ops):
+    """configs[3]: one M = 16 x 500 launch writes the slabs, splitk_layernorm reads them as 16 windows of 500 rows."""
+    K.check_splitk_layernorm(ops, "cuda", B=16, S=1, T=500, c=1280, flat=True)
+
+
 @pytest.mark.parametrize("case", K.UPNOISE_CASES, ids=lambda c: c["id"])
 def test_upsample_noise_fused(ops, case):
     K.check_upsample_noise(ops, case, device="cuda")
@@ -195,6 +200,13 @@ def test_conv_gemm_two_deep_ring_is_bit_identical(ops, tile, n, cin, k, T):
 @pytest.mark.parametrize("n,cin,k,T,partials", [(200, 64, 3, 300, False), (70, 40, 5, 150, False), (160, 128, 1, 260, True)])
 def test_conv_gemm_eight_wave_tile_equals_the_four_wave_tile(ops, n, cin, k, T, partials):
     K.check_conv_w8(ops, "cuda", n, cin=cin, k=k, T=T, partials=partials)
+
+
+@pytest.mark.parametrize("case", K.WHISPER_FLAT, ids=lambda c: c["id"])
+def test_conv_gemm_flattened_whisper_projections_same_bits_on_every_tile(ops, case):
+    """The flattened configs[3] projections (M = 8000) give the same bits on the 64x64, 128x64 and 128x128 tiles: all three walk K with
+    the same 32x32x2 MFMA sequence -- what lets a flattened batch item equal the batch run unflattened."""
+    K.check_conv_w8(ops, "cuda", case["n"], cin=case["cin"], k=1, T=case["T"], B=1, tiles=(1, 2, 3))
 
 
 @pytest.mark.timeout(600)

@@ -54,6 +54,10 @@ def test_splitk_layernorm(ops, S, c):
     K.check_splitk_layernorm(ops, "cpu", S=S, c=c)
 
 
+def test_splitk_layernorm_reads_the_flattened_whisper_slabs(ops):
+    K.check_splitk_layernorm(ops, "cpu", B=3, S=1, T=7, c=128, flat=True)
+
+
 @pytest.mark.parametrize("case", K.UPNOISE_CASES, ids=lambda c: c["id"])
 def test_upsample_noise_fused(ops, case):
     K.check_upsample_noise(ops, case, device="cpu")

@@ -215,3 +215,36 @@ def test_config0_fixture_oracle_reproduces_the_reference(golden_dir):
         wav, _ = O.svc_infer(sd, hp, spk, _t(g["pit"]), ppg2, vec2, rand_ini, src_noise, enc_noises)
     assert wav.shape == g["wave"].shape == (T * 320 - 1,)
     assert np.abs(wav - g["wave"]).max() <= TOL
+
+
+def test_oracle_stages_run_in_fp64():
+    """The fp64 references of tests/engine_cases.check_stages_fp64: at tiny dimensions every stage evaluated on float64 weights and
+    inputs returns float64 and agrees with its own fp32 run to fp32 round-off."""
+    hp = C.tiny_hp()
+    sd = W.make_vits_state(hp, seed=1234)
+    d = I.synth_clip(T=9, hp=hp, seed=4, B=2)
+    d["lengths"][1] = 6
+    ck = W.make_whisper_state(C.WHISPER_TINY_TEST)
+    dims = C.WHISPER_TINY_TEST
+    f64 = lambda t: {k: (v.double() if v.is_floating_point() else v) for k, v in t.items()}
+    sd64, x64, wsd64 = f64(sd), f64(d), f64(ck["model_state_dict"])
+    f0c = O.f0_to_coarse(d["pit"])
+    mask = O.sequence_mask(d["lengths"], 9)
+    mel = (torch.randn(2, 80, 40, generator=torch.Generator().manual_seed(5)) * 0.5).clamp(-1, 1.5)
+    layers = O.whisper_kept_layers(dims)
+    with torch.no_grad():
+        pairs = {
+            "audio_encoder": [O.audio_encoder(wsd, mel, dims["n_audio_head"], layers) for wsd, mel in
+                              ((ck["model_state_dict"], mel), (wsd64, mel.double()))],
+            "pitch2source": [O.pitch2source(s, hp, x["pit"], x["rand_ini"], x["src_noise"]) for s, x in ((sd, d), (sd64, x64))],
+            "text_encoder": [O.text_encoder(s, x["ppg"], x["vec"], f0c, d["lengths"], x["enc_noise"])[0] for s, x in ((sd, d), (sd64, x64))],
+        }
+        z_p = pairs["text_encoder"][0]
+        pairs["flow_reverse"] = [O.flow_reverse(s, zz, mm, x["spk"]) for s, zz, mm, x in ((sd, z_p, mask, d), (sd64, z_p.double(), mask.double(), x64))]
+        z, src = pairs["flow_reverse"][0] * mask, pairs["pitch2source"][0]
+        pairs["generator_inference"] = [O.generator_inference(s, hp, x["spk"], zz, ss) for s, zz, ss, x in
+                                        ((sd, z, src, d), (sd64, z.double(), src.double(), x64))]
+    for name, (o32, o64) in pairs.items():
+        assert o32.dtype == torch.float32 and o64.dtype == torch.float64, name
+        err = float((o32.double() - o64).abs().max()) / max(1.0, float(o64.abs().max()))
+        assert 0.0 < err <= 2e-6, (name, err)

@@ -263,14 +263,19 @@ class Ops:
         self._stage_call("svcmi_synth_infer_fwd", ctypes.byref(m), ctypes.byref(io), ws, ws_bytes, self._stream())
         return (wave, parts) if want_parts else wave
 
-    def synth_stages_fwd(self, cm, ppg, vec, pit, spk, lengths, source, noise, *, ppg_row_shift=0, stream_frames=0):
+    def synth_stages_fwd(self, cm, ppg, vec, pit, spk, lengths, source, noise, *, ppg_row_shift=0, stream_frames=0, flow_in=None,
+                         gen_in=None):
         """The same forward pass as ``synth_infer_fwd`` through the three per-stage entry points (svcmi_text_encoder_fwd ->
         svcmi_flow_reverse_fwd -> svcmi_generator_fwd), for callers that want the intermediate tensors.  Returns (wave, z_p, z);
-        z_p / z time-major [B, T, inter]."""
-        self._chk(ppg, vec, pit, spk, lengths, source, noise)
+        z_p / z time-major [B, T, inter].  ``flow_in`` / ``gen_in`` (time-major [B, T, inter]): start the flow / the generator from
+        this tensor instead of the previous stage's output (stage-by-stage parity tests)."""
+        self._chk(ppg, vec, pit, spk, lengths, source, noise, flow_in, gen_in)
         m = cm.struct
         m.lp_min_flops = max(float(self.lp_min_flops), 1e-30)
         B, T = pit.shape
+        for t_ in (flow_in, gen_in):
+            if t_ is not None and (tuple(t_.shape) != (B, T, m.inter) or not t_.is_contiguous() or t_.dtype != torch.float32):
+                raise SvcmiError(f"expected a contiguous fp32 stage input of shape {(B, T, m.inter)}, got {tuple(t_.shape)}")
         need = self.lib.svcmi_synth_workspace_bytes(ctypes.byref(m), B, T, int(stream_frames))
         if need < 0:
             raise SvcmiError(f"svcmi_synth_workspace_bytes failed with code {need}")
@@ -282,9 +287,10 @@ class Ops:
         io.wave = _ptr(wave)
         z_p = torch.empty(B, T, m.inter, dtype=torch.float32, device=pit.device)
         self._stage_call("svcmi_text_encoder_fwd", ctypes.byref(m), ctypes.byref(io), _ptr(z_p), ws, ws_bytes, self._stream())
-        z = z_p.clone()
+        z = (z_p if flow_in is None else flow_in).clone()           # the flow runs in place
         self._stage_call("svcmi_flow_reverse_fwd", ctypes.byref(m), ctypes.byref(io), _ptr(z), ws, ws_bytes, self._stream())
-        self._stage_call("svcmi_generator_fwd", ctypes.byref(m), ctypes.byref(io), _ptr(z), ws, ws_bytes, self._stream())
+        self._stage_call("svcmi_generator_fwd", ctypes.byref(m), ctypes.byref(io), _ptr(z if gen_in is None else gen_in), ws, ws_bytes,
+                         self._stream())
         return wave, z_p, z
 
     def trace_begin(self, max_records=8192):
