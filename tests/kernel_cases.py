@@ -16,7 +16,7 @@ import torch.nn.functional as F
 from oracle import svc_oracle as O
 from workload import weights as W
 from svcmi import weights as PW
-from svcmi.ops import ACT_GELU, ACT_MISH, ACT_NONE, ACT_RELU, ACT_TANH, SPLIT16
+from svcmi.ops import ACT_GELU, ACT_MISH, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, SPLIT16
 
 
 def _g(seed):
@@ -30,8 +30,39 @@ def _close(got, want, tol, what=""):
     assert err <= tol * scale, f"{what}: max-abs err {err:.3e} (scale {scale:.2f}) > {tol:.1e}"
 
 
+U32 = 2.0 ** -24          # half an ulp of 1 in fp32: the relative error of ONE correctly rounded fp32 operation
+RULE_A_FACTOR = 8.0       # the factor of the stage bars (tests/test_gpu_stage_parity.py)
+
+
+def _close64(got, want64, ref32, what="", factor=RULE_A_FACTOR):
+    """Rule A: one kernel against the plain formula in float64, PER ELEMENT.
+
+    ``want64``: the operation's formula in float64 on the same fp32 inputs.  ``ref32``: the same formula in fp32 torch on the CPU, in its
+    best-conditioned form.  a = max_i max(0, |ref32_i - want64_i| - 2^-24 |want64_i|) is the smallest absolute floor at which that fp32
+    reference itself passes at factor 1 -- it measures how ill-conditioned the operation is AT THESE INPUTS and never looks at the kernel.
+    The kernel passes if |got_i - want64_i| <= factor * (2^-24 |want64_i| + a) for every element: an error in a small output is not
+    hidden behind a large one elsewhere in the tensor.  Returns (worst err / tol, a) and prints both."""
+    got = got.detach().cpu()
+    assert got.dtype == torch.float32 and want64.dtype == torch.float64 and ref32.dtype == torch.float32, what
+    assert got.shape == want64.shape == ref32.shape, (what, got.shape, want64.shape, ref32.shape)
+    assert bool(torch.isfinite(want64).all()) and bool(torch.isfinite(ref32).all()), f"{what}: the reference is not finite"
+    w = want64.abs()
+    a = ((ref32.double() - want64).abs() - U32 * w).clamp_min(0.0).max().item()
+    tol = factor * (U32 * w + a)
+    err = (got.double() - want64).abs()
+    err = torch.where(torch.isfinite(err), err, torch.full_like(err, float("inf")))          # NaN / Inf out of the kernel: fails
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / tol)                          # (err > 0 at tol == 0: inf)
+    worst = ratio.max().item()
+    print(f"[rule A] {what}: a = {a:.3e}  worst err/tol = {worst:.3f}")
+    if not worst <= 1.0:
+        i = int(ratio.flatten().argmax())
+        raise AssertionError(f"{what}: |got - want| = {err.flatten()[i]:.3e} > {factor:g} * (2^-24 |want| + a) = {tol.flatten()[i]:.3e} "
+                             f"(ratio {worst:.2f}, a = {a:.2e}) at flat index {i}: want {want64.flatten()[i]:.9e}, got {got.flatten()[i]:.9e}")
+    return worst, a
+
+
 _ACT = {ACT_NONE: lambda v: v, ACT_RELU: torch.relu, ACT_GELU: F.gelu,
-        ACT_MISH: lambda v: v * torch.tanh(F.softplus(v)), ACT_TANH: torch.tanh}
+        ACT_MISH: lambda v: v * torch.tanh(F.softplus(v)), ACT_TANH: torch.tanh, ACT_SIGMOID: torch.sigmoid}
 
 # id, B, T, Cin, N, K, stride, dil, pad, act, res, alpha, accumulate, lengths, mask_in, mask_out, repeat, tile
 CONV_CASES_SMALL = [
@@ -535,19 +566,20 @@ ATTN_CASES_LARGE = [
 ]
 
 
-def attention_reference(qkv, H, scale, rel_k, rel_v, W, lengths):
+def attention_eval(qkv, H, scale, rel_k, rel_v, W, lengths, dtype=torch.float64):
+    """The attention formula (vits/attentions.py, whisper/model.py) evaluated entirely in ``dtype``; returns [B, T, C] in ``dtype``."""
     B, T, C3 = qkv.shape
     Cc = C3 // 3
     D = Cc // H
-    q, k, v = [t.view(B, T, H, D).permute(0, 2, 1, 3).double() for t in qkv.split(Cc, dim=-1)]
+    q, k, v = [t.view(B, T, H, D).permute(0, 2, 1, 3).to(dtype) for t in qkv.split(Cc, dim=-1)]
     s = q @ k.transpose(-1, -2)
     idx = torch.arange(T)
     rel = idx[None, :] - idx[:, None]
     if rel_k is not None:
         band = rel.abs() <= W
         relc = (rel + W).clamp(0, 2 * W)
-        qe = q @ rel_k.double().t()
-        s = s + torch.where(band, qe.gather(-1, relc.expand(B, H, T, T)), torch.zeros((), dtype=torch.double))
+        qe = q @ rel_k.to(dtype).t()
+        s = s + torch.where(band, qe.gather(-1, relc.expand(B, H, T, T)), torch.zeros((), dtype=dtype))
     s = s * scale
     if lengths is not None:
         m = (idx[None, :] < lengths[:, None])
@@ -556,22 +588,89 @@ def attention_reference(qkv, H, scale, rel_k, rel_v, W, lengths):
     p = torch.softmax(s, dim=-1)
     o = p @ v
     if rel_k is not None:
-        pb = torch.where(band, p, torch.zeros((), dtype=torch.double))
-        rw = torch.zeros(B, H, T, 2 * W + 1, dtype=torch.double)
+        pb = torch.where(band, p, torch.zeros((), dtype=dtype))
+        rw = torch.zeros(B, H, T, 2 * W + 1, dtype=dtype)
         rw.scatter_add_(-1, relc.expand(B, H, T, T), pb)
-        o = o + rw @ rel_v.double()
-    return o.permute(0, 2, 1, 3).reshape(B, T, Cc).float()
+        o = o + rw @ rel_v.to(dtype)
+    return o.permute(0, 2, 1, 3).reshape(B, T, Cc)
 
 
-def check_attention(ops, c, device):
-    g = _g(7 + c["T"])
+def attention_reference(qkv, H, scale, rel_k, rel_v, W, lengths):
+    return attention_eval(qkv, H, scale, rel_k, rel_v, W, lengths).float()
+
+
+# Peaked logits (rule A).  ``qscale``: q alone is scaled, so the logits have a standard deviation of ~qscale and the running maximum of the
+# online softmax jumps by tens to hundreds of units between key tiles and between the key ranges of the waves -- corr = 2^(m_run - m_new) and
+# the cross-wave cw = 2^(m_w - m_all) really rescale (with N(0, 1) logits both stay within a factor ~e of 1).  ``peak``: constructed -- every
+# query's maximum is the LAST key of the sequence, everything before it >= 200 units lower: the whole accumulated state is rescaled to 0 by
+# the last tile (and by the merge: only the last wave's range holds the maximum) and the output is that key's V row.  ``near_mask``: real
+# scores of about -1e4, the value masked keys are filled with (the reference is defined there: masked keys then carry real weight).
+def _peaked(cases, scales=(8, 30)):
+    out = []
+    for c in cases:
+        out += [dict(c, id=f"{c['id']}_qscale{q}", qscale=float(q)) for q in scales]
+        out.append(dict({k: v for k, v in c.items() if k != "lengths"}, id=f"{c['id']}_peak_last_key", peak=True))
+    return out
+
+
+ATTN_CASES_PEAKED = _peaked([
+    dict(id="pk_plain_d64_T130", B=1, T=130, H=2, D=64, lds=-1),                                    # attention_kernel<64, 2, false>: the maximum in wave 1's range
+    dict(id="pk_wide_d64_T65", B=1, T=65, H=1, D=64, lds=-1, ns=1, wide=1),                         # attention_wide_kernel: a one-key second step
+    dict(id="pk_q32_d64_ragged_T77", B=2, T=77, H=2, D=64, lengths=[77, 40], q32=True),             # attention_q32_kernel
+    dict(id="pk_lds_d64_T300", B=1, T=300, H=2, D=64, lds=1),                                       # attention_lds_kernel<64, 4, 2>
+    dict(id="pk_lds24_d32_T40_empty_ranges", B=1, T=40, H=1, D=32, lds=24),                         # ... key ranges past T: the empty-range guards
+    dict(id="pk_lds82_d64_ragged_T260", B=2, T=260, H=1, D=64, lengths=[200, 260], lds=82),
+    dict(id="pk_lds42_rel_d96_T140", B=1, T=140, H=2, D=96, rel=True, W=4, lds=42),                 # attention_lds_kernel<.., true>: the band
+    dict(id="pk_lds42_rel_d32_ragged_T150", B=2, T=150, H=2, D=32, rel=True, W=4, lengths=[150, 61], lds=42),
+    dict(id="pk_wide_rel_d96_T140_ns2", B=1, T=140, H=2, D=96, rel=True, W=4, lds=-1, ns=2, wide=1),  # attention_wide_kernel<96, 2, true>
+    dict(id="pk_plain_rel_d32_T140_w2", B=1, T=140, H=2, D=32, rel=True, W=2, lds=-1, ns=2),        # attention_kernel<32, 2, true>
+]) + [dict(id="pk_plain_d64_ragged_T77_scores_at_mask_value", B=2, T=77, H=2, D=64, lengths=[77, 50], lds=-1, near_mask=True)]
+
+
+def _attention_inputs(c, g):
+    """qkv (+ band embeddings, lengths) of an attention case; the peaked classes are built on top of the N(0, 1) draw."""
     B, T, H, D = c["B"], c["T"], c["H"], c["D"]
-    qkv = torch.randn(B, T, 3 * H * D, generator=g)
+    Cc = H * D
+    qkv = torch.randn(B, T, 3 * Cc, generator=g)
     rel_k = torch.randn(2 * c["W"] + 1, D, generator=g) * D ** -0.5 if c.get("rel") else None
     rel_v = torch.randn(2 * c["W"] + 1, D, generator=g) * D ** -0.5 if c.get("rel") else None
     lengths = torch.tensor(c["lengths"], dtype=torch.int32) if "lengths" in c else None
     scale = D ** -0.5
-    want = attention_reference(qkv, H, scale, rel_k, rel_v, c.get("W", 0), lengths)
+    q, k = qkv[..., :Cc].view(B, T, H, D), qkv[..., Cc:2 * Cc].view(B, T, H, D)           # views: edits land in qkv
+    if c.get("qscale"):
+        q *= c["qscale"]
+    if c.get("peak") or c.get("near_mask"):
+        u = torch.randn(H, D, generator=g)
+        u = u / u.norm(dim=-1, keepdim=True)
+    if c.get("peak"):          # q_i = 60 u + n_i, k_last = 60 u + n': score 3600 * scale >= 360; the other keys: N(0, (60 scale)^2 + 1) <= ~40
+        q += 60.0 * u
+        k[:, T - 1] += 60.0 * u
+    if c.get("near_mask"):     # q_i = r u + n_i, k_j = -r u + n_j with r^2 * scale = 1e4
+        r = math.sqrt(1.0e4 / scale)
+        q += r * u
+        k -= r * u
+    return qkv, rel_k, rel_v, lengths, scale
+
+
+def _check_peak(c, qkv, scale, want64):
+    """The constructed case is what it claims: the last key leads every query by >= 200 units, and (band-free) the fp64 output IS its V row."""
+    B, T, H, D = c["B"], c["T"], c["H"], c["D"]
+    Cc = H * D
+    q, k = [t.view(B, T, H, D).permute(0, 2, 1, 3).double() for t in (qkv[..., :Cc], qkv[..., Cc:2 * Cc])]
+    s = (q @ k.transpose(-1, -2)) * scale
+    gap = (s[..., T - 1:] - s[..., :T - 1]).min().item()
+    assert gap >= 200.0 + (30.0 if c.get("rel") else 0.0), (c["id"], gap)               # (the band adds |q . E_k| * scale < 30 to in-band keys)
+    if not c.get("rel"):
+        assert torch.equal(want64, qkv[:, T - 1:, 2 * Cc:].double().expand(B, T, Cc)), c["id"]
+
+def check_attention(ops, c, device):
+    g = _g(7 + c["T"])
+    H = c["H"]
+    rule_a = bool(c.get("qscale") or c.get("peak") or c.get("near_mask"))
+    qkv, rel_k, rel_v, lengths, scale = _attention_inputs(c, g)
+    want64 = attention_eval(qkv, H, scale, rel_k, rel_v, c.get("W", 0), lengths)
+    if c.get("peak"):
+        _check_peak(c, qkv, scale, want64)
     dev = lambda t: None if t is None else t.to(device)
     if c.get("q32"):
         assert ops.lib.svcmi_tune_set(b"attn_q32", 1) == 0 and ops.lib.svcmi_tune_set(b"attn_ns", c.get("ns", 0)) == 0
@@ -588,7 +687,9 @@ def check_attention(ops, c, device):
         ops.lib.svcmi_tune_set(b"attn_ns", 0)
         ops.lib.svcmi_tune_set(b"attn_lds", 0)
         ops.lib.svcmi_tune_set(b"attn_wide", -1)
-    _close(got, want, 2e-5, c["id"])
+    if rule_a:
+        return _close64(got, want64, attention_eval(qkv, H, scale, rel_k, rel_v, c.get("W", 0), lengths, dtype=torch.float32), c["id"])
+    _close(got, want64.float(), 2e-5, c["id"])
 
 
 def check_snake(ops, n, c, device, amp=1.5, alpha_mean=0.0):
@@ -1013,16 +1114,27 @@ ATTN16_CASES_LARGE = [
 ]
 
 
+# the peaked-logit classes of ATTN_CASES_PEAKED on the 16-bit kernel, one block shape each way (band-free and band), both formats
+ATTN16_CASES_PEAKED = _peaked([
+    dict(id="a16pk_f16_d64_T130_41", B=1, T=130, H=2, D=64, fmt="f16", shape=41),
+    dict(id="a16pk_bf16_d64_T300_42", B=1, T=300, H=2, D=64, fmt="bf16", shape=42),
+    dict(id="a16pk_f16_d64_ragged_T260_82", B=2, T=260, H=1, D=64, fmt="f16", shape=82, lengths=[200, 260]),
+    dict(id="a16pk_bf16_d32_T40_44_empty_ranges", B=1, T=40, H=1, D=32, fmt="bf16", shape=44),
+    dict(id="a16pk_f16_d96_rel_T67_21", B=1, T=67, H=2, D=96, fmt="f16", shape=21, rel=True, W=4, lengths=[60]),
+    dict(id="a16pk_bf16_d96_rel_T260_24", B=2, T=260, H=2, D=96, fmt="bf16", shape=24, rel=True, W=4, lengths=[260, 201]),
+    dict(id="a16pk_f16_d32_rel_w2_T140_42", B=1, T=140, H=2, D=32, fmt="f16", shape=42, rel=True, W=2, lengths=[133]),
+])
+
+
 def check_attention16(ops, c, device):
     g = _g(31 + c["T"])
-    B, T, H, D = c["B"], c["T"], c["H"], c["D"]
+    H = c["H"]
     dt = torch.float16 if c["fmt"] == "f16" else torch.bfloat16
-    qkv16 = torch.randn(B, T, 3 * H * D, generator=g).to(dt)
-    lengths = torch.tensor(c["lengths"], dtype=torch.int32) if "lengths" in c else None
-    scale = D ** -0.5
-    rel_k = torch.randn(2 * c["W"] + 1, D, generator=g) * D ** -0.5 if c.get("rel") else None
-    rel_v = torch.randn(2 * c["W"] + 1, D, generator=g) * D ** -0.5 if c.get("rel") else None
-    want = attention_reference(qkv16.float(), H, scale, rel_k, rel_v, c.get("W", 0), lengths)        # fp64 attention of the SAME 16-bit operands
+    qkv, rel_k, rel_v, lengths, scale = _attention_inputs(c, g)
+    qkv16 = qkv.to(dt)
+    want64 = attention_eval(qkv16.float(), H, scale, rel_k, rel_v, c.get("W", 0), lengths)        # fp64 attention of the SAME 16-bit operands
+    if c.get("peak"):
+        _check_peak(c, qkv16.float(), scale, want64)
     assert ops.lib.svcmi_tune_set(b"attn16", int(c["shape"])) == 0
     dev = lambda t: None if t is None else t.to(device)
     try:
@@ -1031,7 +1143,7 @@ def check_attention16(ops, c, device):
         ops.lib.svcmi_tune_set(b"attn16", 0)
     assert torch.equal(o16.cpu(), o.cpu().to(dt)), c["id"]
     # the only rounding left is P -> 16 bits before the PV product: rel. 2^-11 (f16) / 2^-8 (bf16) per probability
-    _close(o, want, 1.5e-3 if c["fmt"] == "f16" else 1.2e-2, c["id"])
+    _close(o, want64.float(), 1.5e-3 if c["fmt"] == "f16" else 1.2e-2, c["id"])
 
 
 def check_kernels_in_flight_beside_fp16_half_step(ops, victim="alias", replays=8, launches=30, culprit_launches=60):
@@ -1122,3 +1234,437 @@ def check_kernels_in_flight_beside_fp16_half_step(ops, victim="alias", replays=8
     finally:
         if tuned:
             assert ops.lib.svcmi_tune_set(b"amp_mfma", 1) == 0
+
+
+# ============================================================================================== numeric edges, rule A (_close64)
+# Every check below feeds ONE kernel the inputs where kernels go wrong -- the tails and switch points of the hand-written transcendentals,
+# ill-conditioned reductions, exact data movement -- and compares per element against the plain formula in float64.
+
+def _f32_neighbours(v, k=3):
+    """v rounded to fp32 and its k fp32 neighbours on either side."""
+    t = torch.tensor([v], dtype=torch.float32)
+    out, up, dn = [t], t, t
+    for _ in range(k):
+        up, dn = torch.nextafter(up, torch.tensor([math.inf])), torch.nextafter(dn, torch.tensor([-math.inf]))
+        out += [up, dn]
+    return torch.cat(out)
+
+
+# switch points of the activation code (csrc/svcmi_rt.h svcmi_gelu, csrc/conv_gemm_body.h act_apply): GELU's fitted range ends at
+# |v| / sqrt 2 = 4.2; Mish: softplus threshold 20 and u = fl(1 + e^v) == 1 from v = ln 2^-24 = -16.64 down; tanhf's branches at 9 and 90
+ACT_SWITCHES = (4.2 * math.sqrt(2.0), 20.0, 24.0 * math.log(2.0), 9.0, 90.0)
+
+
+def act_sweep(fp16=False):
+    """[1, 4096, 8] activation arguments: dense over [-14, 14], log-spaced magnitudes up to 1e6 (fp16: up to 65504) of both signs, +-0,
+    subnormals, and the neighbours of every switch in ACT_SWITCHES on both sides of 0.  ``fp16``: every value exactly representable in fp16."""
+    lin = torch.arange(-14 * 64, 14 * 64 + 1, dtype=torch.float32) / 64.0 if fp16 else torch.linspace(-14.0, 14.0, 14001)
+    mags = torch.logspace(-8, 6, 561)
+    sub = torch.tensor([1.401298464e-45, 1.0e-40, 5.877471754e-39, 1.175494211e-38, 1.175494351e-38])      # min subnormal .. min normal
+    parts = [lin, mags, -mags, sub, -sub, torch.tensor([0.0, -0.0])]
+    for sw in ACT_SWITCHES:
+        for sgn in (1.0, -1.0):
+            parts.append(_f32_neighbours(sgn * sw))
+    v = torch.cat(parts)
+    if fp16:
+        h = v[v.abs() <= 65504.0].half()
+        nb = []
+        for sw in ACT_SWITCHES:                       # the fp16 neighbours of the switches: +-3 steps of the fp16 bit pattern
+            for sgn in (1.0, -1.0):
+                bits = torch.tensor([sgn * sw]).half().view(torch.int16)
+                nb.append(torch.cat([(bits + d).view(torch.float16) for d in range(-3, 4)]))
+        h = torch.cat([h, torch.tensor([65504.0, -65504.0, 2.0 ** -24, -2.0 ** -24, 2.0 ** -15]).half()] + nb)
+        v = h.float()
+        assert torch.equal(v.half().float(), v)
+    assert v.numel() <= 4096 * 8
+    return torch.cat([v, torch.zeros(4096 * 8 - v.numel())]).view(1, 4096, 8)
+
+
+def _gelu_erfc(v):
+    """GELU in its best-conditioned plain form, in v's dtype: 0.5 v erfc(-v / sqrt 2) (no 1 + erf cancellation in the negative tail)."""
+    return 0.5 * v * torch.special.erfc(-v / math.sqrt(2.0))
+
+
+ACT_FORMULAS = {           # act -> (float64 formula, fp32 reference); None: the operation is exact
+    ACT_GELU: (_gelu_erfc, _gelu_erfc),
+    ACT_MISH: (lambda v: v * torch.tanh(torch.logaddexp(v, torch.zeros_like(v))), lambda v: v * torch.tanh(F.softplus(v))),
+    ACT_TANH: (torch.tanh, torch.tanh),
+    ACT_SIGMOID: (torch.sigmoid, torch.sigmoid),
+    ACT_RELU: None,
+    ACT_NONE: None,
+}
+
+
+def _identity_conv(ops, x, act, device, fp16=False, bias=None):
+    """act(x + bias) through the GEMM epilogue: k = 1, c_in = n = 8, identity weight (1 * x + seven exact zeros: the pre-activation IS x)."""
+    n = x.shape[-1]
+    wp = PW.pack_conv(torch.eye(n).view(n, n, 1)).to(device)
+    xd = x.to(device)
+    if not fp16:
+        return ops.conv(xd, wp, None if bias is None else bias.to(device), ksize=1, act=act, split_k=1)
+    saved, ops.lp_min_flops = ops.lp_min_flops, 0.0
+    try:
+        with ops.use_precision("f16"):
+            y, y16 = ops.conv(xd, wp, None, ksize=1, act=act, split_k=1, x16=xd.half(), out16=torch.float16)
+    finally:
+        ops.lp_min_flops = saved
+    assert getattr(wp, "_svcmi_lp", None) and wp._svcmi_lp.get(PRECISIONS["f16"] + 2) is not None, "the 16-bit-activation kernel did not run"
+    assert torch.equal(y16.cpu(), y.cpu().half()), "the 16-bit output copy is not the rounded fp32 output"
+    return y
+
+
+def check_act_pointwise(ops, act, device, fp16=False):
+    """One activation epilogue over act_sweep(), per element (rule A); ReLU / none are exact (-0 == 0 as values)."""
+    x = act_sweep(fp16)
+    y = _identity_conv(ops, x, act, device, fp16)
+    if ACT_FORMULAS[act] is None:
+        assert torch.equal(y.cpu(), torch.relu(x) if act == ACT_RELU else x), f"act {act}"
+        return None
+    f64, f32 = ACT_FORMULAS[act]
+    return _close64(y, f64(x.double()), f32(x), f"act {act} pointwise{' (f16 operands)' if fp16 else ''}")
+
+
+def check_gelu_infinities(ops, device):
+    """gelu(+inf) = +inf, gelu(-inf) = 0 (either sign), finite neighbours untouched: values, no NaN.  The infinities come in through the bias
+    (x = 0: the other channels of the row stay finite)."""
+    bias = torch.tensor([math.inf, -math.inf, 0.0, 1.0, math.inf, -math.inf, -1.0, 3.0e38])
+    y = _identity_conv(ops, torch.zeros(1, 5, 8), ACT_GELU, device, bias=bias).cpu()
+    want = _gelu_erfc(bias.double()[[2, 3, 6]]).float()
+    for r in range(5):
+        assert y[0, r, 0] == math.inf and y[0, r, 4] == math.inf and y[0, r, 1] == 0.0 and y[0, r, 5] == 0.0 and y[0, r, 7] == bias[7], y[0, r]
+        assert torch.allclose(y[0, r, [2, 3, 6]], want, rtol=0, atol=1e-6)
+
+
+def check_gelu_through_channel_norm(ops, device, T=700, c=8):
+    """svcmi_gelu as channel_norm_gelu calls it: ramps whose normalised values, times gamma, span [-12, 12] (channel 0) down to [-1.5, 1.5]."""
+    t = torch.linspace(-1.0, 1.0, T)
+    x = torch.stack([t * (1.0 + 0.25 * ch) + 0.1 * ch for ch in range(c)], dim=-1)[None].contiguous()
+    span = float((t / t.std(unbiased=False)).abs().max())
+    gamma = torch.tensor([12.0 / span / (ch + 1) for ch in range(c)])
+    beta = torch.tensor([0.0, 0.25, -0.25, 0.5, -0.5, 1.0, -1.0, 0.0])[:c]
+    gn = lambda v, dt: F.group_norm(v.to(dt).transpose(1, 2), c, gamma.to(dt), beta.to(dt), 1e-5).transpose(1, 2)
+    n64 = gn(x, torch.float64)
+    assert n64[..., 0].max() > 11.9 and n64[..., 0].min() < -11.9
+    got = ops.channel_norm_gelu(x.to(device), gamma.to(device), beta.to(device))
+    return _close64(got, _gelu_erfc(n64), _gelu_erfc(gn(x, torch.float32)), "gelu through channel_norm_gelu")
+
+
+# ---------------------------------------------------------------------------------------------- B2: SnakeAlias range reduction
+def _hold_filter():
+    """A 12-tap 'filter' that makes SnakeAlias pointwise and EXACT around the activation: taps 5 and 6 = 1/2.  The polyphase up-sampler then
+    is a zero-order hold, (s_up[2t], s_up[2t+1]) = (x[t], x[t]) with no rounding (2 * 0.5 * x), and the decimator returns
+    0.5 s_up[2t] + 0.5 s_up[2t+1] = snake(x[t]) with no rounding either: the sin^2 argument is the fp32 input times a, where the test put it."""
+    f = torch.zeros(12)
+    f[5] = f[6] = 0.5
+    return f
+
+
+def _snake_edge_inputs(n, c):
+    """x [1, n, c] and per-channel classes for the range-reduction checks (c >= 10).  Levels + a ramp of 7 rad so that every phase of sin^2
+    is visited.  Channel classes:  'sharp': 1e2, 1e3, 1e4 rad with a = 1;  'switch': 0.9e5 / 1.1e5 alternating in time -- with the hold filter
+    a register pair is (s_up[2t-1], s_up[2t]) = (x[t-1], x[t]), so the pair straddles the 1e5 switch, below-above in one channel and above-below
+    in the other;  'huge': everything above 1e5."""
+    ramp = torch.linspace(0.0, 7.0, n)
+    alt = (torch.arange(n) % 2).float()
+    x = torch.zeros(1, n, c)
+    x[0, :, 0], x[0, :, 1], x[0, :, 2] = 1.0e2 + ramp, 1.0e3 + ramp, 1.0e4 + ramp
+    x[0, :, 3] = -1.0e4 - ramp
+    x[0, :, 4] = 0.9e5 + 0.2e5 * alt + ramp           # below, above, below, ...
+    x[0, :, 5] = 1.1e5 - 0.2e5 * alt + ramp           # above, below, above, ...
+    x[0, :, 6], x[0, :, 7] = 2.0e5 + 100.0 * ramp, -7.0e5 - 1.0e3 * ramp
+    x[0, :, 8], x[0, :, 9] = 3.0e3 + ramp, 0.95e5 + 1.0e3 * ramp       # alpha != 0 below
+    return x, dict(sharp=[0, 1, 2, 3], switch=[4, 5], huge=[6, 7], scaled=[8, 9])
+
+
+def check_snake_range_reduction(ops, device, fused=False, n=64):
+    """sin^2 range reduction of SnakeAlias (csrc/snake_math.h) at arguments of 1e2 .. 7e5 rad, rule A per channel class.
+
+    With the Kaiser filter of the model the up-sampled value carries its own fp32 rounding (2^-24 * 1e4 = 6e-4 rad at 1e4), which is as
+    large as what a broken reduction adds, and with beta ~ 1 the output is dominated by y itself -- the reference's `a` shows both and the
+    check is coarse.  So the SHARP cases use _hold_filter() (the argument is exactly the fp32 input) and beta_log = -12 (1 / b = 1.6e5: the
+    output is sin^2 magnified, 1e-7 of sin^2 is 0.02 of the output): a dropped pi_lo step (8.7e-8 * n, n = x / pi) is 0.4 / 4 / 44 there.
+    'switch' and 'huge' are coarse by construction (at 1e5 one ulp of the argument is 0.008 rad; in fp32 the argument itself is exact here,
+    so they are judged all the same): their job is to prove that the libm branch and the per-pair fix-up of snake_fn2_all are taken and sane.
+    ``fused``: the same through snake_conv (c = 10, ld = 12, k = 3, centre-tap identity weight)."""
+    c, ld = 10, 12
+    x, cls = _snake_edge_inputs(n, c)
+    al, be = torch.zeros(c), torch.full((c,), -12.0)
+    al[8], al[9] = 0.3, -0.2
+    be[8], be[9] = 0.0, 0.1
+    out = {}
+    for name, filt in (("hold", _hold_filter()), ("kaiser", W.kaiser_sinc_filter().view(-1))):
+        want64 = O.snake_alias(x.double().transpose(1, 2), al.double(), be.double(), filt.double()).transpose(1, 2)
+        ref32 = O.snake_alias(x.transpose(1, 2), al, be, filt).transpose(1, 2)
+        assert want64.dtype == torch.float64 and ref32.dtype == torch.float32
+        if name == "hold":        # the construction holds: the up-sampled argument is the input, pairs straddle the switch in both orders
+            arg = x[0, :, :8]
+            assert ((arg[:-1, 4] < 1e5) & (arg[1:, 4] > 1e5)).any() and ((arg[:-1, 5] > 1e5) & (arg[1:, 5] < 1e5)).any()
+            assert bool((arg[:, 6:8].abs() > 1e5).all()) and bool((arg[:, :4].abs() < 1e5).all())
+        xp = torch.zeros(1, n, ld)
+        xp[..., :c] = x
+        pad = lambda t: torch.cat([t, torch.zeros(ld - c)])
+        if fused:
+            w = torch.zeros(c, c, 3)
+            w[:, :, 1] = torch.eye(c)
+            assert ops.snake_conv_supported(c, ld, 3, 1)
+            got = ops.snake_conv(xp.to(device), pad(al).to(device), pad(be).to(device), filt.to(device), PW.pack_conv(w, ld, ld).to(device),
+                                 torch.zeros(ld).to(device), c=c, ksize=3, dilation=1, out=torch.full((1, n, ld), 7.0).to(device))
+            assert float(got[..., c:].abs().max()) == 0.0
+        else:
+            got = ops.snake_alias(xp.to(device), pad(al).to(device), pad(be).to(device), filt.to(device))
+        got = got.cpu()[..., :c]
+        for k, ch in cls.items():
+            out[(name, k)] = _close64(got[..., ch].contiguous(), want64[..., ch].contiguous(), ref32[..., ch].contiguous(),
+                                      f"snake{'_conv' if fused else '_alias'} {name} filter, {k} channels")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- B3: LayerNorm family
+_ILL_KINDS = ("1e3 + N(0,1)", "1e4 + 1e-2 N(0,1)", "constant 3", "one outlier 1e4", "-1e3 + N(0,1)", "constant 1000", "N(0,1)")
+
+
+def _ill_rows(g, rows, c):
+    """[rows, c] fp32 rows cycling through: offset 1e3 / std 1; offset 1e4 / std 1e-2; constant (3, exactly summable: variance 0, the
+    output is beta bit for bit); one outlier of 1e4 among unit values; offset -1e3 / std 1; constant 1000; plain N(0, 1)."""
+    x = torch.randn(rows, c, generator=g)
+    kind = torch.arange(rows) % 7
+    for r in range(rows):
+        k = int(kind[r])
+        if k == 0: x[r] += 1.0e3
+        elif k == 1: x[r] = x[r] * 1.0e-2 + 1.0e4
+        elif k == 2: x[r] = 3.0
+        elif k == 3: x[r, (5 * r + 1) % c] = 1.0e4
+        elif k == 4: x[r] -= 1.0e3
+        elif k == 5: x[r] = 1000.0
+    return x, (kind == 2) | (kind == 5)
+
+
+def check_layernorm_edges(ops, c, device, rows=7):
+    """svcmi_layernorm_f32 on ill-conditioned rows (see _ill_rows), rule A against float64; constant rows return beta bit for bit.
+    A one-pass E[x^2] - mean^2 variance in fp32 loses the rows with an offset entirely (1e6 * 2^-24 = 0.06 against a variance of 1)."""
+    g = _g(900 + c)
+    x, const = _ill_rows(g, rows, c)
+    x = x.view(1, rows, c)
+    gamma, beta = torch.randn(c, generator=g), torch.randn(c, generator=g)
+    got = ops.layernorm(x.to(device), gamma.to(device), beta.to(device))
+    assert torch.equal(got.cpu()[0, const], beta.expand(int(const.sum()), c)), "constant rows must give beta exactly"
+    want64, ref32 = F.layer_norm(x.double(), (c,), gamma.double(), beta.double(), 1e-5), F.layer_norm(x, (c,), gamma, beta, 1e-5)
+    # every row is its own check: `a` of the offset-1e4 row (~0.1) must not excuse an error in a well-conditioned one
+    return [_close64(got[0, r], want64[0, r], ref32[0, r], f"layernorm edges c={c} row {r} ({_ILL_KINDS[r % 7]})") for r in range(rows)]
+
+
+def check_layernorm_rejects_wide_rows(ops, device):
+    """c = 2052 > 64 lanes x 4 x 8 float4: an error code from the entry point (checked before any launch), not a result."""
+    from svcmi._lib import SvcmiError
+    x = torch.zeros(1, 3, 2052).to(device)
+    try:
+        ops.layernorm(x)
+    except SvcmiError:
+        return
+    raise AssertionError("layernorm accepted c = 2052")
+
+
+def check_splitk_layernorm_edges(ops, device, S, c, B=2, T=4):
+    """svcmi_splitk_layernorm_f32 fed slabs directly: the first slab carries the ill-conditioned rows, the others unit noise (constant rows: 1
+    per slab, bias 2, residual 1 -> the exactly constant 3 + S and beta out).  S = 5: the second group of four slabs."""
+    g = _g(950 + c + S)
+    rows, const = _ill_rows(g, B * T, c)
+    part = torch.randn(B, S, T, c, generator=g)
+    part[:, 0] = rows.view(B, T, c)
+    xres = torch.randn(B, T, c, generator=g)
+    cm = const.view(B, T)
+    part[cm[:, None, :].expand(B, S, T)] = 1.0
+    xres[cm] = 1.0
+    bias = torch.full((c,), 2.0)
+    gamma, beta = torch.randn(c, generator=g), torch.randn(c, generator=g)
+    xd = xres.clone().to(device)
+    got = ops.splitk_layernorm(part.to(device), bias.to(device), xd, gamma.to(device), beta.to(device))
+    x64 = part.double().sum(1) + bias.double() + xres.double()
+    x32 = part[:, 0].clone()
+    for s_ in range(1, S):
+        x32 = x32 + part[:, s_]
+    x32 = (x32 + bias) + xres
+    assert torch.equal(got.cpu()[cm], beta.expand(int(cm.sum()), c)), "constant rows must give beta exactly"
+    y64, y32 = F.layer_norm(x64, (c,), gamma.double(), beta.double(), 1e-5), F.layer_norm(x32, (c,), gamma, beta, 1e-5)
+    out = []
+    for r in range(B * T):          # row by row, as in check_layernorm_edges
+        b, t = divmod(r, T)
+        what = f"S={S} c={c} row {r} ({_ILL_KINDS[r % 7]})"
+        out.append(_close64(xd[b, t], x64[b, t], x32[b, t], "splitk_layernorm residual stream " + what))
+        out.append(_close64(got[b, t], y64[b, t], y32[b, t], "splitk_layernorm edges " + what))
+    return out
+
+
+def check_channel_norm_gelu_edges(ops, device, T, c=8, B=2):
+    """channel_norm_gelu with ill-conditioned CHANNELS (statistics run over time): offset 1e3 / std 1, offset 1e4 / std 1e-2, constant,
+    one outlier of 1e4 (at t = 0), and different statistics per batch item; T = 1 / 3 (fewer rows than time chunks), 65 (straddling), 700.
+    Constant channels (all of them at T = 1) are gelu(beta) in every row.  An fp32 E[x^2] - mean^2 in the finalise loses the offset channels."""
+    g = _g(970 + T)
+    x = torch.randn(B, T, c, generator=g)
+    x[0, :, 0] += 1.0e3
+    x[0, :, 1] = x[0, :, 1] * 1.0e-2 + 1.0e4
+    x[0, :, 2] = 3.0
+    x[0, 0, 3] = 1.0e4
+    x[1, :, 0] = x[1, :, 0] * 1.0e-2 - 1.0e4
+    x[1, :, 1] = 1000.0
+    x[1, :, 2] -= 1.0e3
+    x[1, :, 4] *= 30.0
+    gamma, beta = torch.randn(c, generator=g), torch.randn(c, generator=g)
+    got = ops.channel_norm_gelu(x.to(device), gamma.to(device), beta.to(device))
+    gn = lambda v, dt: F.group_norm(v.to(dt).transpose(1, 2), c, gamma.to(dt), beta.to(dt), 1e-5).transpose(1, 2)
+    want64, ref32 = _gelu_erfc(gn(x, torch.float64)), _gelu_erfc(gn(x, torch.float32))
+    gc = got.cpu()
+    # every (item, channel) is its own reduction and its own check
+    r = [_close64(gc[b, :, ch].contiguous(), want64[b, :, ch].contiguous(), ref32[b, :, ch].contiguous(), f"channel_norm_gelu edges T={T} item {b} channel {ch}")
+         for b in range(B) for ch in range(c)]
+    for b, ch in ((0, 2), (1, 1)) + (tuple((b, ch) for b in range(B) for ch in range(c)) if T == 1 else ()):
+        assert bool((gc[b, :, ch] == gc[b, 0, ch]).all()), "a constant channel must give one value"
+        assert abs(float(gc[b, 0, ch]) - float(_gelu_erfc(beta[ch].double()))) <= 8 * (U32 * abs(float(beta[ch])) + 2.7e-7), (b, ch)
+    return r
+
+
+# ---------------------------------------------------------------------------------------------- B5: front-end glue
+def check_reflect_pad(ops, device):
+    """svcmi_reflect_pad_f32 == F.pad(mode='reflect'), exactly: B = 3, n in {2, 5, 401}, pad in {0, 1, n - 1}; pad = n is rejected by the entry
+    point before any launch."""
+    from svcmi._lib import SvcmiError
+    g = _g(41)
+    for n in (2, 5, 401):
+        x = torch.randn(3, n, generator=g)
+        for pad in (0, 1, n - 1):
+            got = ops.reflect_pad(x.to(device), pad)
+            assert torch.equal(got.cpu(), F.pad(x[:, None], (pad, pad), mode="reflect")[:, 0] if pad else x), (n, pad)
+        try:
+            ops.reflect_pad(x.to(device), n)
+        except SvcmiError:
+            continue
+        raise AssertionError(f"reflect_pad accepted pad = n = {n}")
+
+
+def check_power_spectrum(ops, device):
+    """svcmi_power_spectrum_f32: rows = 7, nbins = 201, half = 204, ldri = 408, ldp = 204, with NON-zero input pad columns: re^2 + im^2
+    (rule A), output pad columns exactly 0."""
+    g = _g(42)
+    ri = torch.randn(1, 7, 408, generator=g) * torch.logspace(-3, 3, 7)[None, :, None]
+    got = ops.power_spectrum(ri.to(device), 201, 204).cpu()
+    assert tuple(got.shape) == (1, 7, 204) and float(got[..., 201:].abs().max()) == 0.0
+    re, im = ri[..., :201], ri[..., 204:405]
+    # row by row: the rows span six decades, and `a` of the largest must not excuse the smallest
+    return [_close64(got[0, r, :201], re[0, r].double() ** 2 + im[0, r].double() ** 2, re[0, r] * re[0, r] + im[0, r] * im[0, r], f"power_spectrum row {r}")
+            for r in range(7)]
+
+
+def check_logmel_finish(ops, device, t, c=80):
+    """svcmi_logmel_finish_f32, B = 3 with DIFFERENT maxima per item: item 1's maximum 6 decades above item 0's, item 2 entirely below the 1e-10
+    clamp (a constant comes out).  log10, the PER-ITEM max - 8 floor, (x + 4) / 4, transposed output; mel_power is left holding its log10."""
+    g = _g(43 + t)
+    mp = torch.rand(3, t, c, generator=g) * torch.logspace(-9, 0, c)[None, None, :] + 1e-12
+    mp[1] *= 1.0e6
+    mp[2] = torch.rand(t, c, generator=g) * 1.0e-11
+    mp[0, t // 2, 7], mp[1, t - 1, c - 1] = 3.0, 5.0e6          # the items' maxima, in different blocks of the reduction
+    f = lambda v: torch.log10(v.clamp_min(1e-10))
+    def fin(lg):
+        floor = lg.amax(dim=(1, 2), keepdim=True) - 8.0
+        return ((torch.maximum(lg, floor) + 4.0) / 4.0).transpose(1, 2).contiguous()
+    lg64, lg32 = f(mp.double()), f(mp)
+    assert abs((lg64[1].max() - lg64[0].max()).item() - 6.0) < 0.3 and lg64[2].max().item() == -10.0
+    assert bool((lg64[0] < lg64[0].max() - 8.0).any()) and bool((lg64[1] < lg64[1].max() - 8.0).any())        # the floor is active in both
+    mpd = mp.clone().to(device)
+    got = ops.logmel_finish(mpd)
+    assert tuple(got.shape) == (3, c, t)
+    assert bool((got.cpu()[2] == got.cpu()[2, 0, 0]).all()), "an item below the clamp comes out as one constant"          # ((-10 + 4) / 4: rule A below)
+    r1 = _close64(mpd, lg64, lg32, f"logmel_finish t={t}: mel_power <- log10")
+    r2 = _close64(got, fin(lg64), fin(lg32), f"logmel_finish t={t}: output")
+    return r1, r2
+
+
+def check_crepe_frames(ops, device, n=3000, hop=160, ld=1536):
+    """svcmi_crepe_frames_f32: frames of 1024 samples centred on k * hop, zero-filled past either end, minus their mean, over their UNBIASED
+    std clamped at 1e-10; 254 zero columns either side even in a buffer pre-filled with 7.  The same frames fetched in two calls
+    (frame0 > 0) give the same bits; a silent stretch gives zeros, not Inf / NaN."""
+    g = _g(44)
+    audio = torch.randn(n, generator=g) * 0.3 + 0.05
+    audio[1200:2400] = 0.0                                      # frame 11 (samples 1248 .. 2271) is all silence
+    frames = 1 + n // hop                                       # 19: frames 0 .. 3 overhang the start, 16 .. 18 the end
+    ad = audio.to(device)
+    got = ops.crepe_frames(ad, hop, 0, frames, ld)
+    # the wrapper allocates with torch.empty: run again into memory that held 7.0 by fetching the split halves into one pre-filled buffer
+    buf = torch.full((frames, ld), 7.0).to(device)
+    for f0, cnt in ((0, 7), (7, frames - 7)):
+        ops._call("svcmi_crepe_frames_f32", ad.data_ptr(), n, hop, f0, cnt, buf[f0:].data_ptr(), ld, ops._stream())
+    assert torch.equal(buf, got), "frames fetched as two calls differ from one call"
+    gc = got.cpu()
+    assert float(gc[:, :254].abs().max()) == 0.0 and float(gc[:, 254 + 1024:].abs().max()) == 0.0
+    assert float(gc[11].abs().max()) == 0.0, "a silent frame must come out as zeros"
+    pad = torch.cat([torch.zeros(512), audio, torch.zeros(512 + hop)])
+    fr = pad.unfold(0, 1024, hop)[:frames]
+    assert bool((fr[0, :512] == 0).all()) and bool((fr[frames - 1, -392:] == 0).all())
+    norm = lambda v: (v - v.mean(1, keepdim=True)) / v.std(1, keepdim=True).clamp_min(1e-10)
+    return _close64(gc[:, 254:254 + 1024].contiguous(), norm(fr.double()), norm(fr), "crepe_frames")
+
+
+def check_viterbi_loglik(ops, device):
+    """viterbi_loglik_kernel: log(softmax(p[lo:hi]) + tiny) in range, log(tiny) outside (rule A); frames: random sigmoid outputs, all in-range
+    values equal, one value 80 above the rest (rest 10, peak 90: exp(90) overflows fp32 unless the maximum is subtracted first)."""
+    from svcmi.pitch import inference as PI
+    g = _g(45)
+    lo, hi = PI._frequency_to_bins(50.0), PI._frequency_to_bins(1000.0, ceil=True)
+    prob = torch.sigmoid(3.0 * torch.randn(6, 360, generator=g))
+    prob[1] = 0.5
+    prob[2] = 10.0 + 0.1 * torch.randn(360, generator=g)
+    prob[2, lo + 17] = 90.0
+    prob[3, :lo] = 50.0                                          # large values OUTSIDE the range must not count
+    tiny = float(np.finfo(np.float32).tiny)
+    lt = torch.from_numpy(np.log(PI._transition() + tiny))
+    _, lp = ops.viterbi_decode(prob.to(device), lt.to(device), 4, lo, hi, return_loglik=True)
+    def ref(p):
+        out = torch.full_like(p, 0.0)
+        out[:, lo:hi] = torch.softmax(p[:, lo:hi], dim=1)
+        return torch.log(out + tiny)
+    return _close64(lp, ref(prob.double()), ref(prob), "viterbi log-likelihood")
+
+
+def check_small_reductions(ops, device):
+    """block_mean, segment_mean (empty and single-row segments) and row_sqnorm (d = 4 and 1280, rows of magnitude 1e3) directly, rule A."""
+    g = _g(46)
+    out = {}
+    xs = [torch.randn(3, 10, 4, generator=g) * s for s in (1.0, 1.0e3, 1.0e-3)]
+    for cnt in (1, 2, 3):
+        got = ops.block_mean([t.to(device) for t in xs[:cnt]])
+        s64, s32 = xs[0].double(), xs[0]
+        for t in xs[1:cnt]:
+            s64, s32 = s64 + t.double(), s32 + t
+        out[f"block_mean{cnt}"] = _close64(got, s64 / cnt, s32 / float(cnt), f"block_mean of {cnt}")
+    x = torch.randn(20, 8, generator=g) * torch.logspace(-2, 2, 20)[:, None]
+    order = torch.randperm(20, generator=g)[:9].to(torch.int32)
+    off = torch.tensor([0, 0, 1, 4, 4, 9], dtype=torch.int32)        # empty, one row, three rows, empty, five rows
+    dst = torch.full((5, 8), 7.0).to(device)
+    got = ops.segment_mean(x.to(device), order.to(device), off.to(device), dst).cpu()
+    assert bool((got[[0, 3]] == 7.0).all()), "empty segments stay untouched"
+    seg = lambda v, a, b: v[order[a:b].long()].sum(0) / (b - a)
+    w64 = torch.stack([seg(x.double(), a, b) for a, b in ((0, 1), (1, 4), (4, 9))])
+    w32 = torch.stack([seg(x, a, b) for a, b in ((0, 1), (1, 4), (4, 9))])
+    assert torch.equal(got[1], x[order[0].long()]), "a single-row segment is that row"
+    for j, r in enumerate((1, 2, 4)):
+        out[f"segment_mean{r}"] = _close64(got[r], w64[j], w32[j], f"segment_mean segment {r}")
+    for d in (4, 1280):
+        v = torch.randn(6, d, generator=g) * 1.0e3
+        v[5] *= 1.0e-3
+        sq = ops.row_sqnorm(v.to(device)).cpu()
+        for r in range(6):
+            out[f"row_sqnorm{d}_{r}"] = _close64(sq[r:r + 1], (v[r:r + 1].double() ** 2).sum(1), (v[r:r + 1] * v[r:r + 1]).sum(1), f"row_sqnorm d={d} row {r}")
+    return out
+
+
+def check_embed_pitch_unsafe_pitches(ops, device):
+    """f0_to_coarse (vits/utils.py:20-33) for pitches its comparisons do not order -- NaN, and f0 < -700 where log(1 + f0 / 700) is NaN -- and
+    the infinities: the bin clamp must hold (bin 1 = unvoiced, 255 for +inf), never an arbitrary table row.  CPU emulator only: such values
+    are never fed to the GPU test."""
+    assert device == "cpu"
+    pit = torch.tensor([[math.nan, -800.0, -700.0, -math.inf, math.inf, -1.0e30, 1.0e30, 0.0, 440.0, -699.99]])
+    want_bin = torch.tensor([1, 1, 1, 1, 255, 1, 255, 1, int(O.f0_to_coarse(torch.tensor([440.0]))[0]), 1])
+    g = _g(47)
+    x, emb = torch.randn(1, pit.shape[1], 8, generator=g), torch.randn(256, 8, generator=g)
+    xd = x.clone()
+    ops.embed_pitch(xd, pit, emb, torch.tensor([pit.shape[1]], dtype=torch.int32))
+    assert torch.equal(xd, x + emb[want_bin][None]), "embed_pitch read another table row"

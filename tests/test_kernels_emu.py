@@ -205,3 +205,88 @@ def test_conv_gemm_two_deep_ring_is_bit_identical(ops, tile, n, cin, k, T):
 @pytest.mark.parametrize("n,cin,k,T,partials", [(200, 64, 3, 300, False), (70, 40, 5, 150, False), (160, 128, 1, 260, True)])
 def test_conv_gemm_eight_wave_tile_equals_the_four_wave_tile(ops, n, cin, k, T, partials):
     K.check_conv_w8(ops, "cpu", n, cin=cin, k=k, T=T, partials=partials)
+
+
+# ---------------------------------------------------------------------------------------------- numeric edges against float64 (rule A)
+_ACT_IDS = {K.ACT_GELU: "gelu", K.ACT_MISH: "mish", K.ACT_TANH: "tanh", K.ACT_SIGMOID: "sigmoid", K.ACT_RELU: "relu", K.ACT_NONE: "none"}
+
+
+@pytest.mark.parametrize("act", list(_ACT_IDS), ids=lambda a: _ACT_IDS[a])
+def test_activation_epilogue_pointwise(ops, act):
+    K.check_act_pointwise(ops, act, "cpu")
+
+
+@pytest.mark.parametrize("act", [K.ACT_GELU, K.ACT_SIGMOID], ids=lambda a: _ACT_IDS[a])
+def test_activation_epilogue_pointwise_f16_operands(ops, act):
+    K.check_act_pointwise(ops, act, "cpu", fp16=True)
+
+
+def test_gelu_of_infinities_is_the_limit(ops):
+    K.check_gelu_infinities(ops, "cpu")
+
+
+def test_gelu_through_channel_norm_spans_the_fitted_range(ops):
+    K.check_gelu_through_channel_norm(ops, "cpu")
+
+
+@pytest.mark.parametrize("fused", [False, True], ids=["snake_alias", "snake_conv"])
+def test_snake_range_reduction(ops, fused):
+    K.check_snake_range_reduction(ops, "cpu", fused=fused)
+
+
+@pytest.mark.parametrize("c", [4, 64, 260, 2048])
+def test_layernorm_ill_conditioned_rows(ops, c):
+    K.check_layernorm_edges(ops, c, "cpu")
+
+
+def test_layernorm_rejects_rows_wider_than_it_holds(ops):
+    K.check_layernorm_rejects_wide_rows(ops, "cpu")
+
+
+@pytest.mark.parametrize("S,c", [(1, 4), (5, 4), (1, 2048), (5, 2048)])
+def test_splitk_layernorm_ill_conditioned_rows(ops, S, c):
+    K.check_splitk_layernorm_edges(ops, "cpu", S, c)
+
+
+@pytest.mark.parametrize("T", [1, 3, 65, 700])
+def test_channel_norm_gelu_ill_conditioned_channels(ops, T):
+    K.check_channel_norm_gelu_edges(ops, "cpu", T)
+
+
+@pytest.mark.parametrize("case", K.ATTN_CASES_PEAKED, ids=lambda c: c["id"])
+def test_attention_peaked_logits(ops, case):
+    K.check_attention(ops, case, device="cpu")
+
+
+@pytest.mark.parametrize("case", K.ATTN16_CASES_PEAKED, ids=lambda c: c["id"])
+def test_attention16_peaked_logits(ops, case):
+    K.check_attention16(ops, case, "cpu")
+
+
+def test_reflect_pad(ops):
+    K.check_reflect_pad(ops, "cpu")
+
+
+def test_power_spectrum(ops):
+    K.check_power_spectrum(ops, "cpu")
+
+
+@pytest.mark.parametrize("t", [5, 33, 1700])
+def test_logmel_finish_per_item_maxima(ops, t):
+    K.check_logmel_finish(ops, "cpu", t)
+
+
+def test_crepe_frames(ops):
+    K.check_crepe_frames(ops, "cpu")
+
+
+def test_viterbi_loglik(ops):
+    K.check_viterbi_loglik(ops, "cpu")
+
+
+def test_block_mean_segment_mean_row_sqnorm(ops):
+    K.check_small_reductions(ops, "cpu")
+
+
+def test_embed_pitch_clamps_the_bin_of_unordered_pitches(ops):
+    K.check_embed_pitch_unsafe_pitches(ops, "cpu")

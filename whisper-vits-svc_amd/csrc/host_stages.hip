@@ -382,7 +382,9 @@ void whisper_fwd(Ctx& c, const svcmi_whisper_model& m, const float* mel, const f
     // items of tw rows -- M tiles then span batch items (16 x 500 rows = 63 tiles of 128 rows instead of 16 x 4 with 12 padded rows each:
     // -1.6 % matrix-pipe time).  Rows are independent and keep their K order: the same bits.  (Every tensor of the block is [B][tw][C]
     // without gaps; the row count stays inside the 2^27-element window of the kernels' 32-bit buffer offsets.)
-    const bool flat = B > 1 && (int64_t)B * tw > small_m && (int64_t)B * tw * (F > 3 * S ? F : 3 * S) < (1LL << 27);
+    // (One launch over B * tw rows writes its split-K slabs as [1][S][B*tw][C], which splitk_layernorm reads as [B][S][tw][C]: the same
+    // bytes only without K slices, so flattening REQUIRES so == sm == 1 -- today implied by the small_m branch above, stated here.)
+    const bool flat = B > 1 && (int64_t)B * tw > small_m && so == 1 && sm == 1 && (int64_t)B * tw * (F > 3 * S ? F : 3 * S) < (1LL << 27);
     const int rb = flat ? 1 : B, rt = flat ? B * tw : tw;
     for (int i = 0; i < nb; ++i) {
         const svcmi_whisper_block& blk = m.blocks[i];

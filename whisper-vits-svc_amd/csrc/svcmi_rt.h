@@ -297,7 +297,11 @@ __device__ __forceinline__ void svcmi_buf_store16(svcmi_f32x4 v, svcmi_brsrc r, 
 // Whisper MLP-up launch were its epilogue's GELU.  Here: t = |v| / sqrt 2, erfc(t) = 2^(t * q(t)) with q a degree-7 polynomial fitted to
 // log2(erfc(t)) / t on [0, 4.2] under the weight erfc(t) (max |erf error| 1.6e-8, scripts/fit_gelu.py), ONE v_exp_f32, and
 //   v > 0:  v - (0.5 v) erfc(t)        v <= 0:  (0.5 v) erfc(t)
-// which needs no 1 - erfc cancellation: max |error| 2.7e-7 over [-12, 12] against the fp64 function (torch's own fp32 GELU: 1.2e-6).
+// which needs no 1 - erfc cancellation: max |error| 2.7e-7 over |v| < 4.2 sqrt 2 = 5.94 against the fp64 function (torch's own fp32
+// GELU: 1.2e-6).  From |v| / sqrt 2 = 4.2 on (erfc(4.2) = 3e-9: below half an ulp of 1, and |v| erfc / 2 < 9e-9 and falling) the
+// function IS its limit in fp32 and a select returns it: v for v > 0, -0 for v < 0 -- exact for every finite |v| however large and
+// for +-inf (the fitted form gave |v| * 1.5e-9 at v < 0 and inf - inf at +inf).  NaN stays NaN: it fails the `a >= 4.2` compare and
+// takes the fitted form.
 #ifndef SVCMI_EMU
 __device__ __forceinline__
 #else
@@ -315,7 +319,8 @@ float svcmi_gelu(float v) {
     q = fmaf(q, t, -0.9184163808822632f);
     q = fmaf(q, t, -1.6279085874557495f);
     const float h = 0.5f * v * svcmi_exp2(q * t);
-    return v > 0.f ? v - h : h;
+    const float fit = v > 0.f ? v - h : h, tail = v > 0.f ? v : -0.f;
+    return a >= 4.2f ? tail : fit;
 }
 
 // Four consecutive values as a 16-bit copy (8-byte store): fmt 0 bf16, 1 f16, 2 split bf16 -- hi = rne(x) at dst, lo = rne(x - hi) at

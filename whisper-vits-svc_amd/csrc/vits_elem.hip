@@ -119,7 +119,9 @@ __device__ __forceinline__ int f0_to_coarse_dev(float f0) {
     const float mel_span = 986.6532669978451f;
     float mel = 1127.0f * logf(1.0f + f0 / 700.0f);
     if (mel > 0.f) mel = (mel - mel_min) * 254.0f / mel_span + 1.0f;
-    if (mel <= 1.f) mel = 1.f;
+    // the clamp, written so that it also holds for what the reference's comparisons let through: f0 < -700 or NaN gives mel = NaN, every
+    // compare with NaN is false and (int)NaN is undefined -- `!(mel > 1)` sends it to bin 1 (unvoiced) instead of an arbitrary table row
+    if (!(mel > 1.f)) mel = 1.f;
     if (mel > 255.f) mel = 255.f;
     return (int)(mel + 0.5f);
 }

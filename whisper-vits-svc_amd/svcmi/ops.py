@@ -664,9 +664,10 @@ class Ops:
         fmt16_of() on the C side)."""
         return {PREC_BF16: torch.bfloat16, PREC_F16: torch.float16, _lib.PREC_F16W2: torch.float16, PREC_BF16X3: SPLIT16}.get(self.precision)
 
-    def viterbi_decode(self, prob, log_trans, batch_frames, minidx, maxidx, band=0):
+    def viterbi_decode(self, prob, log_trans, batch_frames, minidx, maxidx, band=0, return_loglik=False):
         """prob [frames, 360] (sigmoid outputs), log_trans [360, 360] float64 -> decoded bins int32 [frames].
-        ``band`` > 0: entries with |i - j| > band are one constant (see ``transition_band``)."""
+        ``band`` > 0: entries with |i - j| > band are one constant (see ``transition_band``).
+        ``return_loglik``: also return the per-frame log-likelihoods the dynamic programme read, fp32 [frames, 360] (tests)."""
         self._chk(prob, log_trans)
         Fr = prob.shape[0]
         lp = torch.empty(Fr * 360, dtype=torch.float32, device=prob.device)
@@ -674,7 +675,7 @@ class Ops:
         path = torch.empty(Fr, dtype=torch.int32, device=prob.device)
         self._call("svcmi_viterbi_decode", _ptr(prob), _ptr(log_trans), _ptr(lp), _ptr(ptr), _ptr(path), Fr, batch_frames,
                    minidx, maxidx, band, self._stream())
-        return path
+        return (path, lp.view(Fr, 360)) if return_loglik else path
 
     # ------------------------------------------------------------------ feature retrieval
     def row_sqnorm(self, x):
