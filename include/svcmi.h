@@ -383,6 +383,23 @@ int svcmi_reflect_pad_f32(const float* x, float* y, int32_t batch, int64_t n, in
 int svcmi_power_spectrum_f32(const float* ri, float* p, int64_t rows, int32_t nbins, int32_t half, int32_t ldri, int32_t ldp, void* stream);
 int svcmi_logmel_finish_f32(float* mel_power, float* scratch, float* out, int32_t batch, int32_t t, int32_t c, void* stream);
 
+/* Any-rate wav input (whisper/audio.py:24-26, librosa.load(file, sr=16000)): PCM decode, channel downmix and rational resampling
+ * by up / down in one launch (added under ABI 22: purely additive).
+ *   pcm:  `frames` interleaved frames of `channels` (1..8) samples as the file holds them; fmt 0 = float32 (as is), 1 = int16 (/ 2^15),
+ *         2 = int32 ((float)v / 2^31), 3 = uint8 ((v - 128) / 128).  A frame's channels are summed in channel order in fp32 and
+ *         divided by (float)channels (bit-equal to numpy's float32 mean(axis=1) for up to 7 channels).
+ *   taps: the low-pass h (2 * half + 1 values, already scaled by up) packed by phase: taps[p * taps_per_phase + k] = h[p + k * up], 0 past
+ *         the end of h; taps_per_phase = ceil((2 * half + 1) / up).  With c = m * down + half, p = c mod up, j = c div up:
+ *             out[m] = sum_{k < taps_per_phase} x[j - k] * taps[p * taps_per_phase + k],      x = 0 outside [0, frames)
+ *         accumulated with fmaf in ascending k -- scipy.signal.resample_poly's output for its own default filter, to fp32 rounding.
+ *         taps == NULL (only with up == down == 1): decode + downmix only.
+ *   out:  n_out = ceil(frames * up / down) floats.
+ * SVCMI_EINVAL before anything is launched for null pcm / out, frames <= 0, an unknown fmt, channels outside 1..8, up or down < 1,
+ * another n_out, taps == NULL with up != 1 or down != 1, another taps_per_phase; SVCMI_EALIGN for a pcm / taps / out pointer that is
+ * not aligned to its element; SVCMI_EUNSUPPORTED for taps_per_phase > 4096 (down / up beyond ~200). */
+int svcmi_pcm_resample_f32(const void* pcm, int32_t fmt, int32_t channels, int64_t frames, const float* taps, int32_t up, int32_t down,
+                           int32_t taps_per_phase, int32_t half, float* out, int64_t n_out, void* stream);
+
 /* CREPE F0 extractor glue (row N3; the six convolutions and the classifier are svcmi_conv_gemm_f32 launches):
  *   crepe_frames: crepe/core.py:664-703 -- frame f = samples [f*hop - 512, f*hop + 512) of the waveform (zeros outside
  *                 [0, n)), minus its mean, divided by max(1e-10, unbiased std).  Written as rows of `ld` (>= 1532, % 4 == 0)

@@ -196,6 +196,7 @@ SIGNATURES = {
     "svcmi_reflect_pad_f32": (c_int, [_P, _P, _I, _L, _I, _P]),
     "svcmi_power_spectrum_f32": (c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),
     "svcmi_logmel_finish_f32": (c_int, [_P, _P, _P, _I, _I, _I, _P]),
+    "svcmi_pcm_resample_f32": (c_int, [_P, _I, _I, _L, _P, _I, _I, _I, _I, _P, _L, _P]),
     "svcmi_crepe_frames_f32": (c_int, [_P, _L, _I, _I, _I, _P, _I, _P]),
     "svcmi_bn_maxpool2_f32": (c_int, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _I, _I, _P]),
     "svcmi_viterbi_decode": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),

@@ -106,7 +106,8 @@ def pred_vec(model, wavPath, vecPath, device):
 
 @torch.no_grad()
 def units_windowed(model, audio, max_batch=8):
-    """The reference's 20 s window loop (hubert/inference.py:31-48); consecutive windows of equal length run as one batch."""
+    """The reference's 20 s window loop (hubert/inference.py:31-48); consecutive windows of equal length run as one batch.
+    ``audio``: numpy [n], or a tensor [n] already on the device (its windows are stacked there)."""
     plan = window_plan(audio.shape[0])
     out, i = [], 0
     while i < len(plan):
@@ -114,7 +115,10 @@ def units_windowed(model, audio, max_batch=8):
         while j < len(plan) and j - i < max_batch and plan[j][1] - plan[j][0] == plan[i][1] - plan[i][0]:
             j += 1
         # (numpy, not torch, on the host: a torch CPU op on a many-core box wakes its whole intra-op thread pool -- milliseconds per call)
-        wav = torch.from_numpy(np.ascontiguousarray(np.stack([audio[s:e] for (s, e) in plan[i:j]])[:, None, :]))
+        if torch.is_tensor(audio):
+            wav = torch.stack([audio[s:e] for (s, e) in plan[i:j]])[:, None, :]
+        else:
+            wav = torch.from_numpy(np.ascontiguousarray(np.stack([audio[s:e] for (s, e) in plan[i:j]])[:, None, :]))
         out.extend(model.units(wav))
         i = j
     return torch.cat(out, 0)

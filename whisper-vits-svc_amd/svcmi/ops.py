@@ -639,6 +639,25 @@ class Ops:
         self._call("svcmi_logmel_finish_f32", _ptr(mel_power), _ptr(scratch), _ptr(out), B, T, Cc, self._stream())
         return out
 
+    def pcm_resample(self, pcm, fmt, channels, taps, up, down, half):
+        """Interleaved PCM frames as a wav file holds them (``pcm``: flat or [frames, channels]; ``fmt`` 0 float32, 1 int16, 2 int32,
+        3 uint8) -> mono float32 [ceil(frames * up / down)]: decode, downmix and polyphase resampling in one launch
+        (svcmi_pcm_resample_f32).  ``taps``: the packed filter image [up, K] of ``svcmi.whisper.audio.resample_taps`` with its
+        ``half``; None (with up == down == 1) decodes and downmixes only."""
+        self._chk(pcm, taps)
+        pcm = pcm.contiguous()
+        if 0 <= fmt <= 3 and pcm.element_size() != (4, 2, 4, 1)[fmt]:
+            raise SvcmiError(f"pcm_resample: fmt {fmt} does not describe a {pcm.dtype} tensor")
+        if taps is not None and not (taps.dtype == torch.float32 and taps.is_contiguous() and taps.dim() == 2 and taps.shape[0] == up):
+            raise SvcmiError("pcm_resample: taps must be a contiguous float32 [up, K] image")
+        frames = pcm.numel() // max(int(channels), 1)
+        n_out = -(-frames * up // down) if up >= 1 and down >= 1 else 0
+        out = torch.empty(max(n_out, 0), dtype=torch.float32, device=pcm.device)
+        self._call("svcmi_pcm_resample_f32", _ptr(pcm), fmt, channels, frames, _ptr(taps), up, down,
+                   taps.shape[1] if taps is not None else 0, half, _ptr(out), n_out, self._stream(),
+                   work={"bytes": float(pcm.numel() * pcm.element_size() + 4 * n_out)})
+        return out
+
     # ------------------------------------------------------------------ CREPE glue
     def crepe_frames(self, audio, hop, frame0, frames, ld=1536):
         """audio [n] -> normalised, first-layer-padded frames [frames, ld] (crepe/core.py:664-703)."""

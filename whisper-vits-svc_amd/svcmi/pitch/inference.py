@@ -153,7 +153,7 @@ def decode(prob, fmin=50.0, fmax=1000.0, decoder="viterbi", dither=None):
 
 @torch.no_grad()
 def compute_f0_sing(filename, device, model=None, noise=None, dither=None, decoder="viterbi"):
-    """pitch/inference.py:74-99.  ``filename``: wav path or a 16 kHz float waveform [n]; ``model``: a ``Crepe`` (the
+    """pitch/inference.py:74-99.  ``filename``: wav path or a 16 kHz float waveform [n] (numpy, or a tensor on any device); ``model``: a ``Crepe`` (the
     reference loads crepe/assets/full.pth on first use).  ``noise`` [n] ~ N(0,1) pins the 1e-3 input noise (:77),
     ``dither`` [frames] pins convert.py:58-64.  Returns np.float32 Hz [2 * (1 + n // 320)]."""
     return compute_f0_sing_begin(filename, device, model=model, noise=noise, decoder=decoder)(dither)

@@ -142,7 +142,8 @@ def svc_infer(model, retrieval, spk, pit, ppg, vec, hp, device, noise=None, writ
 
 @torch.no_grad()
 def extract_features(audio, whisper, hubert, crepe, device, in_flight=True):
-    """The three extractors of svc_inference.py:138-154 on ONE 16 kHz waveform (numpy float32 [n]), in process and in flight together:
+    """The three extractors of svc_inference.py:138-154 on ONE 16 kHz waveform (numpy float32 [n], or the device tensor of
+    ``whisper.audio.load_audio_device``: then no extractor copies it from the host), in process and in flight together:
     the reference runs them as three child processes one after the other; they are independent, so here the Whisper PPG, the HuBERT
     units and the CREPE F0 track are issued on three HIP streams (clips-in-flight idea of svcmi/lanes.py: one network's launch gaps
     are filled by another's kernels).  Returns (ppg [T50, ppg_dim] device, vec [T50, vec_dim] device, f0 np.float32 [2 * (1 + n // 320)])
@@ -161,6 +162,8 @@ def extract_features(audio, whisper, hubert, crepe, device, in_flight=True):
         side.append(torch.cuda.Stream(device=dev))
     for s in side:
         s.wait_stream(cur)
+        if torch.is_tensor(audio) and audio.is_cuda:
+            audio.record_stream(s)                # made on the current stream, read by the side streams' kernels
     f0_finish = pitch_inf.compute_f0_sing_begin(audio, dev, model=crepe)       # the longest of the three first, on the current stream
     with torch.cuda.stream(side[0]):
         ppg = whisper_inf.ppg_from_audio(whisper, audio)
@@ -226,10 +229,11 @@ def main(args):
     if args.ppg is None and args.vec is None and args.pit is None:
         # all three features from the wav: the extractors run in flight together (extract_features); the intermediate files keep
         # their names and formats
-        from .whisper.audio import load_audio
+        from .whisper.audio import load_audio, load_audio_device
         crepe = pitch_inf.load_crepe(args.crepe, device)
         crepe.precision = f0_prec
-        ppg_d, vec_d, f0 = extract_features(load_audio(args.wave), _with_prec(whisper_inf.load_model(args.whisper, device)),
+        audio = load_audio_device(args.wave, device=device) if getattr(args, "loader", "host") == "gpu" else load_audio(args.wave)
+        ppg_d, vec_d, f0 = extract_features(audio, _with_prec(whisper_inf.load_model(args.whisper, device)),
                                             _with_prec(hubert_inf.load_model(args.hubert, device)), crepe, device)
         args.ppg, args.vec, args.pit = "svc_tmp.ppg.npy", "svc_tmp.vec.npy", "svc_tmp.pit.csv"
         np.save(args.ppg, ppg_d.cpu().numpy(), allow_pickle=False)
@@ -287,6 +291,10 @@ def build_parser():
     p.add_argument("--hubert", type=str, default=os.path.join("hubert_pretrain", "hubert-soft-0d54a1f4.pt"))
     p.add_argument("--crepe", type=str, default=os.path.join("crepe", "assets", "full.pth"))
     p.add_argument("--debug", action="store_true")
+    p.add_argument("--loader", default="host", choices=["host", "gpu"],
+                   help="where the input wav is decoded, downmixed and resampled to 16 kHz: host = numpy + scipy's polyphase resampler "
+                        "(default); gpu = the file's PCM uploaded once and one kernel launch (the same filter, equal to fp32 rounding), "
+                        "the extractors read the device tensor")
     p.add_argument("--precision", default="f32", choices=["f32", "bf16x3", "bf16", "f16", "mixed"],
                    help="GEMM operand precision of the Whisper / HuBERT encoders and the synthesizer (fp32 accumulation, LayerNorm / softmax / "
                         "SnakeAlias in fp32 in every mode): f32 = the reference CPU path's arithmetic (parity default); bf16x3 = split-bf16, "

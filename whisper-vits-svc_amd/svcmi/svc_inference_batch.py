@@ -81,10 +81,12 @@ class Converter:
         from .svc_inference import DummyRetrieval, shift_pitch, svc_infer
         from .whisper import inference as whisper_inf
         from .svc_inference import extract_features
-        from .whisper.audio import load_audio
+        from .whisper.audio import load_audio, load_audio_device
         # the three extractors in flight together, features kept on the device (the reference's per-file .npy / .csv intermediates
         # carry the same values: float32 arrays and the int()-quantised F0 of the pitch CSV, svc_inference.py:150-154,183)
-        ppg, vec, pit = extract_features(load_audio(wav_path), self.whisper, self.hubert, self.crepe, self.device)
+        gpu_loader = getattr(self.args, "loader", "host") == "gpu" and torch.device(self.device).type == "cuda"
+        audio = load_audio_device(wav_path, device=self.device) if gpu_loader else load_audio(wav_path)
+        ppg, vec, pit = extract_features(audio, self.whisper, self.hubert, self.crepe, self.device)
         ppg = torch.repeat_interleave(ppg, 2, 0)              # np.repeat(ppg, 2, 0), svc_inference.py:175-182
         vec = torch.repeat_interleave(vec, 2, 0)
         pit = torch.FloatTensor(shift_pitch(pitch_inf.quantize_pitch_like_csv(pit), self.args.shift))
@@ -162,6 +164,10 @@ def build_parser():
     p.add_argument("--precision", default="f32", choices=["f32", "bf16x3", "bf16", "f16", "mixed"],
                    help="GEMM operand precision of Whisper / HuBERT / synthesizer (see svc_inference); f32 = parity default")
     p.add_argument("--f0-precision", default="f32", choices=["f32", "bf16x3", "f16", "bf16"], help="GEMM operand precision of the CREPE F0 extractor (see svc_inference)")
+    p.add_argument("--loader", default="host", choices=["host", "gpu"],
+                   help="where the input wav is decoded, downmixed and resampled to 16 kHz: host = numpy + scipy's polyphase resampler "
+                        "(default); gpu = the file's PCM uploaded once and one kernel launch (the same filter, equal to fp32 rounding), "
+                        "the extractors read the device tensor")
     p.add_argument("--workers", type=int, default=3,
                    help="files in flight per GPU: worker threads, each converting its files on its own HIP stream (1 = the reference's order)")
     return p

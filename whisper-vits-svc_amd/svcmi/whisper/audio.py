@@ -12,6 +12,13 @@ pinned against an independent implementation instead (transformers.audio_utils.m
 tests/test_independent_pins.py).  A DOCUMENTED DIVERGENCE remains for non-16 kHz files: ``librosa.load`` resamples with soxr,
 ``load_audio`` with scipy's polyphase filter -- both band-limited resamplers, not the same taps; the test file checks ours
 against analytically sampled tones (16 kHz PCM input, what the reference's own preprocessing writes, is bit-exact).
+
+    load_audio_device(file)     ->  [n] float32 device tensor at 16 kHz, what ``load_audio`` returns, made on the GPU
+
+``load_audio_device`` uploads the file's raw PCM once and makes ONE launch of csrc/resample.hip: decode, channel downmix and the
+SAME polyphase filter (``resample_taps``: scipy's default design, packed by phase) -- equal to ``load_audio`` to fp32 rounding
+against an fp64 evaluation of that filter (bit-equal where no resampling is needed), without the host's resampling milliseconds.
+The extractors take the device tensor as it is (svc_inference.extract_features, ``--loader gpu`` of the two CLIs).
 """
 import math
 from functools import lru_cache
@@ -91,6 +98,62 @@ def load_audio(file, sr=SAMPLE_RATE):
         g = math.gcd(int(rate), int(sr))
         x = resample_poly(x, sr // g, rate // g).astype(np.float32)
     return x
+
+
+PCM_FORMATS = {"float32": 0, "int16": 1, "int32": 2, "uint8": 3}      # numpy dtype name -> svcmi_pcm_resample_f32's fmt
+
+
+def resample_filter(up, down):
+    """The low-pass ``scipy.signal.resample_poly(x, up, down)`` designs by default, in float64:
+    ``h = up * firwin(2 * half + 1, 1 / max(up, down), window=("kaiser", 5.0))`` with ``half = 10 * max(up, down)``, for up / down
+    reduced by their gcd.  Returns (h, half, up, down) with the reduced pair."""
+    from scipy.signal import firwin
+    g = math.gcd(int(up), int(down))
+    up, down = int(up) // g, int(down) // g
+    half = 10 * max(up, down)
+    return up * firwin(2 * half + 1, 1.0 / max(up, down), window=("kaiser", 5.0)), half, up, down
+
+
+@lru_cache(maxsize=None)
+def _resample_taps(up, down, device):
+    h, half, up, _ = resample_filter(up, down)
+    k = -(-(2 * half + 1) // up)
+    img = np.zeros(up * k, dtype=np.float64)
+    img[:h.shape[0]] = h
+    img = np.ascontiguousarray(img.reshape(k, up).T).astype(np.float32)            # [p, k] = h[p + k * up]
+    return torch.from_numpy(img).to(device), half
+
+
+def resample_taps(up, down, device="cpu"):
+    """The filter of ``resample_filter`` as the kernel reads it: float32 [up, K], ``taps[p, k] = h[p + k * up]`` (0 past the end of h),
+    K = ceil((2 * half + 1) / up), on ``device``; and ``half``.  Made once per (up, down, device)."""
+    g = math.gcd(int(up), int(down))
+    return _resample_taps(int(up) // g, int(down) // g, str(torch.device(device)))
+
+
+def load_audio_device(file, sr=SAMPLE_RATE, device="cuda", ops=None):
+    """``load_audio`` on the GPU: the wav file's PCM frames are uploaded as they are (int16: half the bytes of a float32 copy) and ONE
+    kernel launch on the current stream decodes, downmixes and resamples them -> float32 [n] on ``device`` at ``sr``.  Same decode
+    arithmetic, same filter; equal to ``load_audio`` bit for bit at the file's own rate, to fp32 rounding otherwise."""
+    from scipy.io import wavfile
+    from ..ops import Ops
+    rate, x = wavfile.read(file)
+    if x.dtype == np.float64:
+        x = x.astype(np.float32)
+    fmt = PCM_FORMATS.get(x.dtype.name)
+    if fmt is None:
+        raise ValueError(f"{file}: {x.dtype} PCM is not supported by the GPU loader (float32 / float64 / int16 / int32 / uint8)")
+    ops = ops if ops is not None else Ops()
+    x = np.ascontiguousarray(x)
+    if not x.flags.writeable:
+        x = x.copy()
+    pcm = torch.from_numpy(x).to(device)
+    channels = 1 if x.ndim == 1 else x.shape[1]
+    if int(rate) == int(sr):
+        return ops.pcm_resample(pcm, fmt, channels, None, 1, 1, 0)
+    g = math.gcd(int(rate), int(sr))
+    taps, half = resample_taps(sr // g, rate // g, device)
+    return ops.pcm_resample(pcm, fmt, channels, taps, sr // g, rate // g, half)
 
 
 @torch.no_grad()

@@ -129,11 +129,15 @@ def window_plan(n_samples, sr=16000, window_s=K.WHISPER_WINDOW_S):
 
 @torch.no_grad()
 def ppg_from_audio(whisper, wav):
-    """whisper/inference.py:32-62 on a 16 kHz float waveform (numpy [n]): log-mel front-end on the GPU, 15 s windows, encoder, kept
+    """whisper/inference.py:32-62 on a 16 kHz float waveform (numpy [n], or a device tensor [n] as ``audio.load_audio_device`` returns
+    it: the windows are then views, nothing is copied from the host): log-mel front-end on the GPU, 15 s windows, encoder, kept
     frames -> device tensor [T50, n_state].  Nothing here waits for the device."""
     from . import audio
     plan = window_plan(wav.shape[0])
-    mels = [audio.log_mel_spectrogram(torch.from_numpy(wav[s:e]), ops=whisper.ops, device=whisper.device) for (s, e, _) in plan]
+    if torch.is_tensor(wav):
+        mels = [audio.log_mel_spectrogram(wav[s:e], ops=whisper.ops, device=whisper.device) for (s, e, _) in plan]
+    else:
+        mels = [audio.log_mel_spectrogram(torch.from_numpy(wav[s:e]), ops=whisper.ops, device=whisper.device) for (s, e, _) in plan]
     return pred_ppg_from_mel(whisper, mels, [k for (_, _, k) in plan])
 
 
