@@ -400,6 +400,34 @@ int svcmi_logmel_finish_f32(float* mel_power, float* scratch, float* out, int32_
 int svcmi_pcm_resample_f32(const void* pcm, int32_t fmt, int32_t channels, int64_t frames, const float* taps, int32_t up, int32_t down,
                            int32_t taps_per_phase, int32_t half, float* out, int64_t n_out, void* stream);
 
+/* Speaker encoder (row N5; speaker/models/lstm.py, speaker/utils/audio.py -- added under ABI 22: purely additive).
+ *   lstm_step:  ONE time step t of one nn.LSTM layer for all batch rows (gate order i, f, g, o; zero initial state):
+ *                   G = gx[b][t][:] + h_{t-1}[b] * W_hh^T;   c = sigmoid(f) c + sigmoid(i) tanh(g);   h_t = sigmoid(o) tanh(c)
+ *               gx:   [batch][t_total][4 * hidden] (batch stride gx_bstride floats) = X * W_ih^T + b_ih + b_hh, columns in TILE ORDER:
+ *                     column 16 * (j / 4) + 4 * gate + j % 4 holds gate `gate` of hidden unit j (a block of the kernel owns 4 units);
+ *               whh:  W_hh [4 * hidden][hidden] with its rows in the same order (row stride = hidden), 16-byte aligned;
+ *               hseq: the layer's output sequence [batch][t_total][ldh]: row t - 1 is read (nothing at t = 0), row t is written;
+ *               c:    the cell state [batch][ldc], updated in place (not read at t = 0).
+ *               The T steps of a layer are T launches in stream order.  K is reduced in a fixed order: a row's bits depend neither on
+ *               the run nor on the batch it is launched in.  Saturated gates give exactly 0 / 1 / +-1, never NaN.
+ *               SVCMI_EINVAL (before any launch): a null pointer, batch / hidden / t_total < 1, t outside [0, t_total), ldh or ldc < hidden,
+ *               strides smaller than a sequence; SVCMI_EUNSUPPORTED: batch > 64; SVCMI_EALIGN: hidden % 4, ldh % 4, h_bstride % 4, whh /
+ *               hseq not 16-byte aligned.
+ *   preemph_pad: y[b][i] = p[reflect(i - pad)], p[n] = x[n] - coef * x[n - 1], p[0] = x[0] (lfilter([1, -coef], [1], x), then the
+ *               reflect padding of a centred STFT); x [batch][n], y [batch][n + 2 * pad], pad < n.
+ *   magnitude_spectrum: as svcmi_power_spectrum_f32, with sqrt(re^2 + im^2).
+ *   speaker_mel_finish: in place on `total` mel-projected magnitudes m: S = 20 log10(max(1e-5, m)) - ref_level_db;
+ *               S = (S - min_level_db) / -min_level_db;  S = 2 max_norm S - max_norm;  clipped to +-max_norm (AudioProcessor.normalize).
+ *   l2norm_rows: y[r][:] = x[r][:] / max(|x[r]|_2, 1e-12) (torch.nn.functional.normalize).
+ *   group_mean: y[g][:] = mean of rows g * rows_per_group .. of x [groups * rows_per_group][d], summed in row order. */
+int svcmi_lstm_step_f32(const float* gx, int64_t gx_bstride, const float* whh, float* hseq, int64_t h_bstride, int32_t ldh,
+                        float* c, int32_t ldc, int32_t batch, int32_t hidden, int32_t t, int32_t t_total, void* stream);
+int svcmi_preemph_pad_f32(const float* x, float* y, int32_t batch, int64_t n, int32_t pad, float coef, void* stream);
+int svcmi_magnitude_spectrum_f32(const float* ri, float* p, int64_t rows, int32_t nbins, int32_t half, int32_t ldri, int32_t ldp, void* stream);
+int svcmi_speaker_mel_finish_f32(float* mel, int64_t total, float ref_level_db, float min_level_db, float max_norm, void* stream);
+int svcmi_l2norm_rows_f32(const float* x, int64_t ldx, int32_t rows, int32_t d, float* y, int64_t ldy, void* stream);
+int svcmi_group_mean_f32(const float* x, int32_t rows_per_group, int32_t groups, int32_t d, float* y, void* stream);
+
 /* CREPE F0 extractor glue (row N3; the six convolutions and the classifier are svcmi_conv_gemm_f32 launches):
  *   crepe_frames: crepe/core.py:664-703 -- frame f = samples [f*hop - 512, f*hop + 512) of the waveform (zeros outside
  *                 [0, n)), minus its mean, divided by max(1e-10, unbiased std).  Written as rows of `ld` (>= 1532, % 4 == 0)
@@ -527,6 +555,29 @@ int64_t svcmi_whisper_workspace_bytes(const svcmi_whisper_model* m, int32_t batc
  * out: [batch][tw][n_state] time-major, tw = (n_frames - 1) / 2 + 1 <= n_ctx (else SVCMI_EINVAL: "incorrect audio shape", :156). */
 int svcmi_whisper_encoder_fwd(const svcmi_whisper_model* m, const float* mel, const float* noise, float noise_scale,
                               int32_t batch, int32_t n_frames, float* out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- LSTMSpeakerEncoder (speaker/models/lstm.py:35-71, use_lstm_with_projection = True): n_layers x [nn.LSTM(d_in, lstm_dim) +
+ * Linear(lstm_dim, proj_dim, bias=False)], the last time step of the last layer L2-normalised.  fp32 only. */
+#define SVCMI_MAX_LSTM_LAYERS 8
+typedef struct svcmi_lstm_layer {
+    svcmi_weight ih;                                /* W_ih [4H][d_in] with bias = b_ih + b_hh, rows in the tile order of svcmi_lstm_step_f32 */
+    svcmi_weight lin;                               /* linear.weight [proj_dim][H], no bias */
+    const float* whh;                               /* W_hh [4H][H], rows in tile order */
+    const void* reserved;
+} svcmi_lstm_layer;
+typedef struct svcmi_speaker_model {
+    int32_t input_dim, lstm_dim, proj_dim, n_layers;
+    svcmi_lstm_layer layers[SVCMI_MAX_LSTM_LAYERS];
+} svcmi_speaker_model;
+
+int64_t svcmi_speaker_encoder_workspace_bytes(const svcmi_speaker_model* m, int32_t batch, int32_t t);
+/* LSTMSpeakerEncoder.inference on mel [batch][t][input_dim] -> emb [batch][proj_dim].  Per layer: one GEMM for the input projections of
+ * all t steps, t launches of svcmi_lstm_step_f32, one GEMM for the output projection (the last layer projects only row t - 1); then
+ * svcmi_l2norm_rows_f32.  Checked before anything is launched: SVCMI_EINVAL for a null pointer, batch < 1, t < 1, n_layers outside
+ * 1..SVCMI_MAX_LSTM_LAYERS, a workspace that is too small or not 256-byte aligned; SVCMI_EUNSUPPORTED for batch > 64 (the caller loops);
+ * SVCMI_EALIGN for lstm_dim / input_dim / proj_dim % 4 or a W_hh that is not 16-byte aligned. */
+int svcmi_speaker_encoder_fwd(const svcmi_speaker_model* m, const float* mel, int32_t batch, int32_t t, float* emb, void* workspace,
+                              int64_t workspace_bytes, void* stream);
 
 /* ---- SynthesizerInfer (vits/models.py:211-256) */
 /* layer classes of the per-layer mixed-precision policy: prior encoder (enc_p: pre / hub / attention + FFN layers / proj, and its attention

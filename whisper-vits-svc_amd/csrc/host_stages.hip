@@ -26,14 +26,15 @@ enum Op {
     OP_CONV_F32, OP_CONV_LP, OP_CONV_GROUP_F32, OP_CONV_GROUP_LP, OP_LAYERNORM, OP_SPLITK_LN, OP_ATTENTION, OP_SNAKE_ALIAS,
     OP_SNAKE_ALIAS_GROUP, OP_BLOCK_MEAN, OP_SNAKE_CONV, OP_SNAKE_CONV_GROUP, OP_UPSAMPLE_NOISE, OP_SNAKE_POST, OP_WN_GATE,
     OP_COUPLING_PRE, OP_COUPLING_POST, OP_EMBED_PITCH, OP_SAMPLE_PRIOR, OP_NCL_TO_NLC, OP_COPY2D, OP_PITCH_PREFIX, OP_PITCH_SOURCE,
-    OP_ATTENTION16, OP_SNAKE_CONV_GROUP_LP, OP_COUNT
+    OP_ATTENTION16, OP_SNAKE_CONV_GROUP_LP, OP_LSTM_STEP, OP_L2NORM_ROWS, OP_COUNT
 };
 const char* const OP_NAMES[OP_COUNT] = {
     "svcmi_conv_gemm_f32", "svcmi_conv_gemm_lp", "svcmi_conv_gemm_group_f32", "svcmi_conv_gemm_group_lp", "svcmi_layernorm_f32",
     "svcmi_splitk_layernorm_f32", "svcmi_attention_f32", "svcmi_snake_alias_f32", "svcmi_snake_alias_group_f32", "svcmi_block_mean_f32",
     "svcmi_snake_conv_f32", "svcmi_snake_conv_group_f32", "svcmi_upsample_noise_f32", "svcmi_snake_post_f32", "svcmi_wn_gate_f32",
     "svcmi_coupling_pre_f32", "svcmi_coupling_post_f32", "svcmi_embed_pitch_f32", "svcmi_sample_prior_f32", "svcmi_ncl_to_nlc_f32",
-    "svcmi_copy2d_f32", "svcmi_pitch_prefix_f64", "svcmi_pitch_source_f32", "svcmi_attention16", "svcmi_snake_conv_group_lp"};
+    "svcmi_copy2d_f32", "svcmi_pitch_prefix_f64", "svcmi_pitch_source_f32", "svcmi_attention16", "svcmi_snake_conv_group_lp",
+    "svcmi_lstm_step_f32", "svcmi_l2norm_rows_f32"};
 
 // ------------------------------------------------------------------------------------------------ per-launch trace (bench.py)
 struct TraceRec {
@@ -849,6 +850,57 @@ void synth_fwd(Ctx& c, const svcmi_synth_model& m, const svcmi_synth_io& io) {
     generator_fwd(c, m, io, zp);
 }
 
+// ------------------------------------------------------------------------------------------------ LSTM speaker encoder
+// speaker/models/lstm.py:35-71.  Per layer: Gx = X W_ih^T + (b_ih + b_hh) for all T steps in one GEMM (its columns already in the
+// step kernel's tile order: the weights were permuted at load), T step launches, then the projection GEMM -- of the whole sequence
+// for an inner layer, of row T - 1 alone for the last one.  fp32 whatever the caller's precision mode.
+int speaker_check(const svcmi_speaker_model& m, int B, int T) {
+    if (B < 1 || T < 1 || m.n_layers < 1 || m.n_layers > SVCMI_MAX_LSTM_LAYERS || m.input_dim < 1 || m.lstm_dim < 1 || m.proj_dim < 1) return SVCMI_EINVAL;
+    for (int l = 0; l < m.n_layers; ++l)
+        if (!m.layers[l].ih.w || !m.layers[l].ih.bias || !m.layers[l].lin.w || !m.layers[l].whh) return SVCMI_EINVAL;
+    if (B > 64) return SVCMI_EUNSUPPORTED;
+    if (m.lstm_dim % 4 || m.input_dim % 4 || m.proj_dim % 4) return SVCMI_EALIGN;
+    for (int l = 0; l < m.n_layers; ++l)
+        if ((uintptr_t)m.layers[l].whh & 15) return SVCMI_EALIGN;
+    return 0;
+}
+
+void speaker_fwd(Ctx& c, const svcmi_speaker_model& m, const float* mel, int B, int T, float* emb) {
+    if (int rc = speaker_check(m, B, T)) { c.rc = rc; return; }
+    const int H = m.lstm_dim, P = m.proj_dim, L = m.n_layers;
+    c.prec = SVCMI_PREC_F32;
+    float* gx = c.ar.f((int64_t)B * T * 4 * H);
+    float* hs = c.ar.f((int64_t)B * T * H);
+    float* cs = c.ar.f((int64_t)B * H);
+    float* y[2] = {L > 1 ? c.ar.f((int64_t)B * T * P) : nullptr, L > 2 ? c.ar.f((int64_t)B * T * P) : nullptr};
+    float* last = c.ar.f((int64_t)B * P);
+    const float* x = mel;
+    int din = m.input_dim;
+    for (int l = 0; l < L; ++l) {
+        const svcmi_lstm_layer& ly = m.layers[l];
+        CV v;
+        v.x = x; v.x_bs = (int64_t)T * din; v.B = B; v.t_in = T; v.c_in = din; v.ldx = din;
+        v.w = &ly.ih; v.n_out = 4 * H; v.y = gx; v.y_bs = (int64_t)T * 4 * H; v.ldy = 4 * H; v.split_k = 1;
+        conv(c, v);
+        for (int t = 0; t < T; ++t)
+            run(c, OP_LSTM_STEP, t ? 8.0 * B * H * (double)H : 0.0, 4.0 * (t ? 4.0 * H * H : 0.0) + 4.0 * B * H * 8.0, [&] {
+                return svcmi_lstm_step_f32(gx, (int64_t)T * 4 * H, ly.whh, hs, (int64_t)T * H, H, cs, H, B, H, t, T, c.stream);
+            });
+        CV p;
+        p.w = &ly.lin; p.bias = false; p.n_out = P; p.c_in = H; p.ldx = H; p.B = B; p.split_k = 1;
+        if (l + 1 < L) {
+            float* out = y[l & 1];
+            p.x = hs; p.x_bs = (int64_t)T * H; p.t_in = T; p.y = out; p.y_bs = (int64_t)T * P; p.ldy = P;
+            conv(c, p);
+            x = out; din = P;
+        } else {
+            p.x = hs + (int64_t)(T - 1) * H; p.x_bs = (int64_t)T * H; p.t_in = 1; p.y = last; p.y_bs = P; p.ldy = P;
+            conv(c, p);
+        }
+    }
+    run(c, OP_L2NORM_ROWS, 0.0, 8.0 * B * P, [&] { return svcmi_l2norm_rows_f32(last, P, B, P, emb, P, c.stream); });
+}
+
 Ctx make_ctx(void* ws, int64_t bytes, void* stream, bool plan) {
     Ctx c;
     c.stream = stream;
@@ -873,6 +925,24 @@ extern "C" int svcmi_whisper_encoder_fwd(const svcmi_whisper_model* m, const flo
     if (workspace_bytes < svcmi_whisper_workspace_bytes(m, batch, n_frames)) return SVCMI_EINVAL;
     Ctx c = make_ctx(workspace, workspace_bytes, stream, false);
     whisper_fwd(c, *m, mel, noise, noise_scale, batch, n_frames, out);
+    return finish(c);
+}
+
+extern "C" int64_t svcmi_speaker_encoder_workspace_bytes(const svcmi_speaker_model* m, int32_t batch, int32_t t) {
+    if (!m) return SVCMI_EINVAL;
+    Ctx c = make_ctx(nullptr, 0, nullptr, true);
+    speaker_fwd(c, *m, nullptr, batch, t, nullptr);
+    return c.rc ? (int64_t)c.rc : c.ar.peak + 256;
+}
+
+extern "C" int svcmi_speaker_encoder_fwd(const svcmi_speaker_model* m, const float* mel, int32_t batch, int32_t t, float* emb, void* workspace,
+                                         int64_t workspace_bytes, void* stream) {
+    if (!m || !mel || !emb || !workspace) return SVCMI_EINVAL;
+    if (int rc = speaker_check(*m, batch, t)) return rc;
+    if (((uintptr_t)workspace & 255) || workspace_bytes < svcmi_speaker_encoder_workspace_bytes(m, batch, t)) return SVCMI_EINVAL;
+    if (((uintptr_t)mel & 15) || ((uintptr_t)emb & 3)) return SVCMI_EALIGN;
+    Ctx c = make_ctx(workspace, workspace_bytes, stream, false);
+    speaker_fwd(c, *m, mel, batch, t, emb);
     return finish(c);
 }
 

@@ -158,6 +158,20 @@ class SynthIO(Structure):
                 ("wave", c_void_p), ("z_p", c_void_p), ("z", c_void_p)]
 
 
+class LstmLayer(Structure):
+    """svcmi_lstm_layer"""
+    _fields_ = [("ih", Weight), ("lin", Weight), ("whh", c_void_p), ("reserved", c_void_p)]
+
+
+MAX_LSTM_LAYERS = 8
+
+
+class SpeakerModel(Structure):
+    """svcmi_speaker_model"""
+    _fields_ = [("input_dim", c_int32), ("lstm_dim", c_int32), ("proj_dim", c_int32), ("n_layers", c_int32),
+                ("layers", LstmLayer * MAX_LSTM_LAYERS)]
+
+
 class TraceRecord(Structure):
     _fields_ = [("op", c_int32), ("ms", c_float), ("flops", c_double), ("bytes", c_double)]
 
@@ -197,6 +211,14 @@ SIGNATURES = {
     "svcmi_power_spectrum_f32": (c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),
     "svcmi_logmel_finish_f32": (c_int, [_P, _P, _P, _I, _I, _I, _P]),
     "svcmi_pcm_resample_f32": (c_int, [_P, _I, _I, _L, _P, _I, _I, _I, _I, _P, _L, _P]),
+    "svcmi_lstm_step_f32": (c_int, [_P, _L, _P, _P, _L, _I, _P, _I, _I, _I, _I, _I, _P]),
+    "svcmi_preemph_pad_f32": (c_int, [_P, _P, _I, _L, _I, _F, _P]),
+    "svcmi_magnitude_spectrum_f32": (c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),
+    "svcmi_speaker_mel_finish_f32": (c_int, [_P, _L, _F, _F, _F, _P]),
+    "svcmi_l2norm_rows_f32": (c_int, [_P, _L, _I, _I, _P, _L, _P]),
+    "svcmi_group_mean_f32": (c_int, [_P, _I, _I, _I, _P, _P]),
+    "svcmi_speaker_encoder_workspace_bytes": (c_int64, [POINTER(SpeakerModel), _I, _I]),
+    "svcmi_speaker_encoder_fwd": (c_int, [POINTER(SpeakerModel), _P, _I, _I, _P, _P, _L, _P]),
     "svcmi_crepe_frames_f32": (c_int, [_P, _L, _I, _I, _I, _P, _I, _P]),
     "svcmi_bn_maxpool2_f32": (c_int, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _I, _I, _P]),
     "svcmi_viterbi_decode": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),

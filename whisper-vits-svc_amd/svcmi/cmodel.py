@@ -54,6 +54,20 @@ def whisper_cmodel(w, ops, prec=PREC_F32):
     return CModel(m, keep)
 
 
+def speaker_cmodel(w, ops):
+    """``w``: svcmi.weights.SpeakerWeights.  fp32 only."""
+    m, keep = _lib.SpeakerModel(), [w]
+    if len(w.layers) > _lib.MAX_LSTM_LAYERS:
+        raise _lib.SvcmiError(f"{len(w.layers)} LSTM layers > {_lib.MAX_LSTM_LAYERS}")
+    m.input_dim, m.lstm_dim, m.proj_dim, m.n_layers = w.input_dim, w.lstm_dim, w.proj_dim, len(w.layers)
+    for i, ly in enumerate(w.layers):
+        _weight(m.layers[i].ih, ops, ly["ih_w"], ly["bias"], PREC_F32, keep)
+        _weight(m.layers[i].lin, ops, ly["lin_w"], None, PREC_F32, keep)
+        m.layers[i].whh = ly["whh"].data_ptr()
+        keep.append(ly["whh"])
+    return CModel(m, keep)
+
+
 def synth_cmodel(w, ops, prec=PREC_F32):
     """``w``: svcmi.weights.VitsWeights.  ``prec``: one mode for every GEMM (an ``enum svcmi_precision`` code) or the
     ``(PREC_MIXED, class modes)`` tuple of ``_lib.parse_precision``: every weight then gets the 16-bit images of ITS class's mode."""

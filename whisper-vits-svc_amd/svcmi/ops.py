@@ -658,6 +658,68 @@ class Ops:
                    work={"bytes": float(pcm.numel() * pcm.element_size() + 4 * n_out)})
         return out
 
+    # ------------------------------------------------------------------ speaker encoder (csrc/lstm.hip)
+    def lstm_step(self, gx, whh, hseq, c, t):
+        """One time step of one LSTM layer, in place: ``gx`` [B, T, 4H] (tile order, biases included), ``whh`` [4H, H] (tile order),
+        ``hseq`` [B, T, H] (row t - 1 read, row t written), ``c`` [B, H] (updated)."""
+        self._chk(gx, whh, hseq, c)
+        B, T, H = hseq.shape
+        self._call("svcmi_lstm_step_f32", _ptr(gx), gx.stride(0), _ptr(whh), _ptr(hseq), hseq.stride(0), hseq.stride(1), _ptr(c), c.stride(0),
+                   B, H, t, T, self._stream(), work={"flops": 8.0 * B * H * H if t else 0.0, "bytes": 16.0 * H * H if t else 0.0})
+        return hseq
+
+    def preemph_pad(self, x, pad, coef):
+        """x [B, n] -> [B, n + 2 pad]: pre-emphasis y[n] = x[n] - coef x[n - 1] (y[0] = x[0]) and reflect padding in one pass."""
+        self._chk(x)
+        B, n = x.shape
+        y = torch.empty(B, n + 2 * pad, dtype=torch.float32, device=x.device)
+        self._call("svcmi_preemph_pad_f32", _ptr(x), _ptr(y), B, n, pad, float(coef), self._stream())
+        return y
+
+    def magnitude_spectrum(self, ri, nbins, half):
+        self._chk(ri)
+        B, T, ld = ri.shape
+        p = torch.empty(B, T, half, dtype=torch.float32, device=ri.device)
+        self._call("svcmi_magnitude_spectrum_f32", _ptr(ri), _ptr(p), B * T, nbins, half, ld, half, self._stream())
+        return p
+
+    def speaker_mel_finish(self, mel, ref_level_db=20.0, min_level_db=-100.0, max_norm=4.0):
+        """In place on the contiguous mel projection: amplitude -> dB, - ref level, range normalisation to +-max_norm, clip."""
+        self._chk(mel)
+        assert mel.is_contiguous()
+        self._call("svcmi_speaker_mel_finish_f32", _ptr(mel), mel.numel(), float(ref_level_db), float(min_level_db), float(max_norm),
+                   self._stream())
+        return mel
+
+    def l2norm_rows(self, x):
+        """x [rows, d] -> x / max(|x|_2, 1e-12) per row."""
+        self._chk(x)
+        y = torch.empty(x.shape[0], x.shape[1], dtype=torch.float32, device=x.device)
+        self._call("svcmi_l2norm_rows_f32", _ptr(x), x.stride(0), x.shape[0], x.shape[1], _ptr(y), y.stride(0), self._stream())
+        return y
+
+    def group_mean(self, x, rows_per_group):
+        """x [groups * rows_per_group, d] (contiguous) -> [groups, d]: the mean of every run of ``rows_per_group`` rows."""
+        self._chk(x)
+        assert x.is_contiguous() and x.shape[0] % rows_per_group == 0
+        y = torch.empty(x.shape[0] // rows_per_group, x.shape[1], dtype=torch.float32, device=x.device)
+        self._call("svcmi_group_mean_f32", _ptr(x), rows_per_group, y.shape[0], x.shape[1], _ptr(y), self._stream())
+        return y
+
+    def speaker_encoder_fwd(self, cm, mel):
+        """LSTMSpeakerEncoder.inference as ONE call: mel [B <= 64, T, input_dim] -> L2-normalised embeddings [B, proj_dim]."""
+        self._chk(mel)
+        m = cm.struct
+        mel = mel.contiguous()
+        B, T, _ = mel.shape
+        need = self.lib.svcmi_speaker_encoder_workspace_bytes(ctypes.byref(m), B, T)
+        if need < 0:
+            raise SvcmiError(f"svcmi_speaker_encoder_workspace_bytes failed with code {need}")
+        ws, ws_bytes = self.stage_workspace(need, mel.device)
+        out = torch.empty(B, m.proj_dim, dtype=torch.float32, device=mel.device)
+        self._stage_call("svcmi_speaker_encoder_fwd", ctypes.byref(m), _ptr(mel), B, T, _ptr(out), ws, ws_bytes, self._stream())
+        return out
+
     # ------------------------------------------------------------------ CREPE glue
     def crepe_frames(self, audio, hop, frame0, frames, ld=1536):
         """audio [n] -> normalised, first-layer-padded frames [frames, ld] (crepe/core.py:664-703)."""

@@ -278,3 +278,47 @@ class CrepeWeights:
             i += 1
         self.fc_w = f(pack_conv(sd["classifier.weight"].float().unsqueeze(-1)))
         self.fc_b = f(sd["classifier.bias"])
+
+
+LSTM_UNIT_TILE = 4      # hidden units per block of csrc/lstm.hip
+
+
+def lstm_tile_order(hidden, unit_tile=LSTM_UNIT_TILE):
+    """Row permutation of an nn.LSTM weight [4H, .] (gate-major: i | f | g | o) into the step kernel's tile order
+    [unit tile][gate][unit]: ``w[perm]`` puts gate ``q`` of hidden unit ``j`` at row ``4 * unit_tile * (j // unit_tile) + unit_tile * q +
+    j % unit_tile``, so the four gate rows of a block's units are one contiguous span."""
+    if hidden % unit_tile:
+        raise ValueError(f"lstm_dim {hidden} is not a multiple of the kernel's unit tile {unit_tile}")
+    j = torch.arange(hidden).view(hidden // unit_tile, 1, unit_tile)
+    q = torch.arange(4).view(1, 4, 1)
+    return (q * hidden + j).reshape(-1)
+
+
+class SpeakerWeights:
+    """Packed ``LSTMSpeakerEncoder`` parameters (speaker/models/lstm.py state-dict keys ``layers.N.lstm.weight_ih_l0`` / ``weight_hh_l0`` /
+    ``bias_ih_l0`` / ``bias_hh_l0`` and ``layers.N.linear.weight``) on one device.  Per layer: ``ih_w`` [4H, d_in] and ``whh`` [4H, H] with
+    their rows in the step kernel's tile order, ``bias`` = b_ih + b_hh in the same order (the input GEMM then writes the gate
+    pre-activations where the step kernel reads them), ``lin_w`` [P, H].  Dimensions are read off the tensors."""
+
+    def __init__(self, sd, device):
+        f = lambda t: t.detach().float().to(device).contiguous()
+        n = 0
+        while f"layers.{n}.lstm.weight_ih_l0" in sd:
+            n += 1
+        if n == 0:
+            raise KeyError("no layers.N.lstm.weight_ih_l0 in the state dict: not an LSTMSpeakerEncoder with projection layers")
+        self.layers = []
+        for i in range(n):
+            p = f"layers.{i}"
+            w_ih, w_hh = sd[p + ".lstm.weight_ih_l0"].float(), sd[p + ".lstm.weight_hh_l0"].float()
+            H = w_hh.shape[1]
+            perm = lstm_tile_order(H).to(w_ih.device)
+            bias = sd[p + ".lstm.bias_ih_l0"].float() + sd[p + ".lstm.bias_hh_l0"].float()
+            self.layers.append(dict(ih_w=f(pack_conv(w_ih[perm].unsqueeze(-1))), whh=f(w_hh[perm]), bias=f(bias[perm]),
+                                    lin_w=f(pack_conv(sd[p + ".linear.weight"].float().unsqueeze(-1)))))
+        self.input_dim = int(sd["layers.0.lstm.weight_ih_l0"].shape[1])
+        self.lstm_dim = int(sd["layers.0.lstm.weight_hh_l0"].shape[1])
+        self.proj_dim = int(sd["layers.0.linear.weight"].shape[0])
+        for d in (self.input_dim, self.lstm_dim, self.proj_dim):
+            if d % 4:
+                raise ValueError(f"speaker encoder dimension {d} is not a multiple of 4")
