@@ -428,6 +428,25 @@ int svcmi_speaker_mel_finish_f32(float* mel, int64_t total, float ref_level_db, 
 int svcmi_l2norm_rows_f32(const float* x, int64_t ldx, int32_t rows, int32_t d, float* y, int64_t ldy, void* stream);
 int svcmi_group_mean_f32(const float* x, int32_t rows_per_group, int32_t groups, int32_t d, float* y, void* stream);
 
+/* Linear spectrogram of a training item (prepare/preprocess_spec.py -> vits/spectrogram.py:41-76, spectrogram_torch with center=False)
+ * in one launch (added under ABI 22: purely additive):
+ *   xp[p] = x[b][reflect(p - pad)], p < n + 2 * pad (F.pad mode="reflect", as index arithmetic on the load: no padded copy);
+ *   out[b][k][t] = sqrt(re^2 + im^2 + eps),  re | im = sum_{i < n_fft} xp[t * hop + i] * basis[i][2k | 2k + 1],  k < bins = n_fft / 2 + 1,
+ *   t < frames = 1 + (n + 2 * pad - n_fft) / hop  (torch.stft without centring).
+ *   x:     [batch][n] fp32, batch stride x_bstride floats (>= n);
+ *   basis: [n_fft][2 * bins] fp32, made by the host in float64 and rounded once: basis[i][2k] = w[i] cos(2 pi ((k i) mod n_fft) / n_fft), the odd
+ *          column with sin; w = the periodic Hann window of win_length, centred and zero padded to n_fft as torch.stft does (the window lives
+ *          in the table, so win_length < n_fft costs nothing);
+ *   out:   [batch][bins][frames] contiguous, the layout the reference saves.
+ * The DFT runs on the fp32 matrix cores (K = n_fft, N = 2 * bins, M = frames).  Every output is one accumulator chain over i in ascending
+ * order followed by sqrtf(fmaf(re, re, fmaf(im, im, eps))): its bits depend on the frame's n_fft padded samples and the table alone, not on the
+ * tile, the number of frames, the batch index or the stream.
+ * SVCMI_EINVAL before anything is launched for a null pointer, batch < 1, hop < 1, pad < 0, an odd n_fft (or < 2), n <= pad (the reference's
+ * reflect pad raises there), n + 2 * pad < n_fft (frames < 1), another `frames`, x_bstride < n with batch > 1; SVCMI_EALIGN for a pointer
+ * that is not 4-byte aligned; SVCMI_EUNSUPPORTED for batch > 65535. */
+int svcmi_linear_spectrogram_f32(const float* x, int64_t x_bstride, int32_t batch, int64_t n, const float* basis, int32_t n_fft, int32_t hop,
+                                 int32_t pad, float eps, float* out, int64_t frames, void* stream);
+
 /* CREPE F0 extractor glue (row N3; the six convolutions and the classifier are svcmi_conv_gemm_f32 launches):
  *   crepe_frames: crepe/core.py:664-703 -- frame f = samples [f*hop - 512, f*hop + 512) of the waveform (zeros outside
  *                 [0, n)), minus its mean, divided by max(1e-10, unbiased std).  Written as rows of `ld` (>= 1532, % 4 == 0)

@@ -211,6 +211,7 @@ SIGNATURES = {
     "svcmi_power_spectrum_f32": (c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),
     "svcmi_logmel_finish_f32": (c_int, [_P, _P, _P, _I, _I, _I, _P]),
     "svcmi_pcm_resample_f32": (c_int, [_P, _I, _I, _L, _P, _I, _I, _I, _I, _P, _L, _P]),
+    "svcmi_linear_spectrogram_f32": (c_int, [_P, _L, _I, _L, _P, _I, _I, _I, _F, _P, _L, _P]),
     "svcmi_lstm_step_f32": (c_int, [_P, _L, _P, _P, _L, _I, _P, _I, _I, _I, _I, _I, _P]),
     "svcmi_preemph_pad_f32": (c_int, [_P, _P, _I, _L, _I, _F, _P]),
     "svcmi_magnitude_spectrum_f32": (c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),

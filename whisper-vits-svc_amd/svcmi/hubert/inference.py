@@ -122,3 +122,13 @@ def units_windowed(model, audio, max_batch=8):
         out.extend(model.units(wav))
         i = j
     return torch.cat(out, 0)
+
+
+@torch.no_grad()
+def pred_vec_train(model, audio):
+    """prepare/preprocess_hubert.py:25-32, the TRAINING recipe: ``model.units`` on the WHOLE clip, no windows -> device tensor [T, proj].
+    ``audio``: wav path, or a 16 kHz float waveform [n] (numpy, or a tensor on any device)."""
+    if isinstance(audio, str):
+        from ..whisper.audio import load_audio
+        audio = load_audio(audio)
+    return model.units(torch.as_tensor(audio, dtype=torch.float32).reshape(1, 1, -1))[0]

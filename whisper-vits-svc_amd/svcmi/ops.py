@@ -658,6 +658,28 @@ class Ops:
                    work={"bytes": float(pcm.numel() * pcm.element_size() + 4 * n_out)})
         return out
 
+    # ------------------------------------------------------------------ linear spectrogram (csrc/spectrogram.hip)
+    def linear_spectrogram(self, x, basis, n_fft, hop, pad, eps=1e-6, out=None):
+        """x [B, n] float32 (unit stride along n, any batch stride) -> STFT magnitudes [B, n_fft // 2 + 1, frames] of the signal reflect-padded
+        by ``pad`` on both sides, frames = 1 + (n + 2 pad - n_fft) // hop, sqrt(re^2 + im^2 + eps): reflect padding, windowed DFT and
+        magnitude in one launch (svcmi_linear_spectrogram_f32).  ``basis``: the [n_fft, n_fft + 2] table of
+        ``svcmi.vits.spectrogram.spectrogram_basis``."""
+        self._chk(x, basis, out)
+        if not (x.dim() == 2 and x.dtype == torch.float32 and (x.shape[1] <= 1 or x.stride(1) == 1)):
+            raise SvcmiError("linear_spectrogram: x must be float32 [B, n] with unit stride along n")
+        bins = n_fft // 2 + 1
+        if not (basis.dtype == torch.float32 and basis.is_contiguous() and tuple(basis.shape) == (n_fft, 2 * bins)):
+            raise SvcmiError("linear_spectrogram: basis must be a contiguous float32 [n_fft, n_fft + 2] table")
+        B, n = x.shape
+        frames = 1 + (n + 2 * pad - n_fft) // hop if hop >= 1 and n + 2 * pad >= n_fft else 0
+        if out is None:
+            out = torch.empty(B, bins, max(frames, 0), dtype=torch.float32, device=x.device)
+        elif not (out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, bins, frames)):
+            raise SvcmiError("linear_spectrogram: out must be a contiguous float32 [B, bins, frames] tensor")
+        self._call("svcmi_linear_spectrogram_f32", _ptr(x), x.stride(0), B, n, _ptr(basis), n_fft, hop, pad, float(eps), _ptr(out), frames,
+                   self._stream(), work={"flops": 4.0 * B * frames * bins * n_fft, "bytes": 4.0 * (B * n + basis.numel() + out.numel())})
+        return out
+
     # ------------------------------------------------------------------ speaker encoder (csrc/lstm.hip)
     def lstm_step(self, gx, whh, hseq, c, t):
         """One time step of one LSTM layer, in place: ``gx`` [B, T, 4H] (tile order, biases included), ``whh`` [4H, H] (tile order),

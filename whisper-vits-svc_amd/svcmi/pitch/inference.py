@@ -251,3 +251,88 @@ def load_csv_pitch(path):
         for line in f.readlines():
             pitch.append(int(line.strip().split(",")[-1]))
     return pitch
+
+
+# ------------------------------------------------------------------------------------------ training recipe (prepare/preprocess_crepe.py)
+TRAIN_HOP = 160
+
+
+def _median_filter_np(x, win_length):
+    """crepe/filter.py:59-106 for one fp32 track in numpy, quirks included: NaNs count as missing, the reflect-padded values come with a
+    ZERO mask (so the first / last windows see fewer valid values), the median is the sorted window's element (valid - 1) // 2, and an
+    infinite result (no valid value, or an infinite input chosen) becomes NaN."""
+    x = np.asarray(x, dtype=np.float32)
+    pad = win_length // 2
+    if x.shape[0] <= pad:
+        raise ValueError(f"median filter of {win_length} needs more than {pad} frames, got {x.shape[0]} (the reference's reflect pad raises)")
+    mask = ~np.isnan(x)
+    xw = np.lib.stride_tricks.sliding_window_view(np.pad(np.where(mask, x, np.float32(0)), pad, mode="reflect"), win_length)
+    mw = np.lib.stride_tricks.sliding_window_view(np.pad(mask, pad, mode="constant", constant_values=False), win_length)
+    srt = np.sort(np.where(mw, xw, np.float32(np.inf)), axis=-1)
+    idx = np.maximum((mw.sum(axis=-1) - 1) // 2, 0)
+    out = np.take_along_axis(srt, idx[:, None], axis=-1)[:, 0].astype(np.float32)
+    out[np.isinf(out)] = np.nan
+    return out
+
+
+def _mean_filter_conv(x, win_length):
+    """crepe/filter.py:10-57 for one fp32 track with the reference's OWN sum: ``F.conv1d`` with a ones kernel on the host.  The five-term
+    window sums of ``_mean_filter_np`` (np.convolve) are added in another order and differ from it in the last bit on ordinary tracks;
+    the training recipe is pinned bit for bit against the reference's filter, so it takes the same operation."""
+    x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).view(1, 1, -1)
+    mask = ~torch.isnan(x)
+    ones = torch.ones(1, 1, win_length)
+    s = torch.nn.functional.conv1d(torch.where(mask, x, torch.zeros_like(x)), ones, stride=1, padding=win_length // 2)
+    c = torch.nn.functional.conv1d(mask.float(), ones, stride=1, padding=win_length // 2).clamp(min=1)
+    out = s / c
+    out[out == 0] = float("nan")
+    return out.view(-1).numpy()
+
+
+def f0_train_postfilter(pitch, periodicity):
+    """prepare/preprocess_crepe.py:40-42 for one track: ``periodicity = median(periodicity, 7)``, ``pitch = mean(pitch, 5)``,
+    ``pitch[periodicity < 0.5] = 0`` -> np.float32 [T].  Tracks shorter than 4 frames raise ValueError."""
+    pitch, periodicity = np.asarray(pitch, dtype=np.float32), np.asarray(periodicity, dtype=np.float32)
+    if pitch.shape != periodicity.shape or pitch.ndim != 1:
+        raise ValueError(f"f0_train_postfilter: pitch {pitch.shape} and periodicity {periodicity.shape} must be equal 1-D tracks")
+    per = _median_filter_np(periodicity, 7)
+    out = _mean_filter_conv(pitch, 5)
+    out[per < np.float32(0.5)] = np.float32(0)
+    return out
+
+
+@torch.no_grad()
+def compute_f0_train(filename, device, model=None, noise=None, dither=None):
+    """prepare/preprocess_crepe.py:11-44 (crepe.predict at hop 160 with return_periodicity, Viterbi, fmin 50 / fmax 1000, then the
+    post-filter above).  ``filename``: wav path or a 16 kHz float waveform [n] (numpy, or a tensor on any device); ``noise`` [n] ~ N(0, 1)
+    pins the 1e-3 input noise (:16), ``dither`` [frames] pins crepe/convert.py:58-64.  Returns np.float32 Hz [1 + n // 160]: 0 where the
+    filtered periodicity is below 0.5, NaN where the mean filter gives NaN."""
+    return compute_f0_train_begin(filename, device, model=model, noise=noise)(dither)
+
+
+@torch.no_grad()
+def compute_f0_train_begin(filename, device, model=None, noise=None):
+    """The device half of ``compute_f0_train``, enqueued on the current stream: network at hop 160, Viterbi on the device in batches of 512
+    frames, periodicity = the network output at every frame's decoded bin (crepe/core.py:710-722) gathered on the device.  Returns
+    ``finish(dither=None)``: ONE device -> host copy (bins and periodicity together), Hz conversion and the post-filter."""
+    if model is None:
+        raise ValueError("pass model=load_crepe(<crepe full.pth>, device)")
+    if isinstance(filename, str):
+        from ..whisper.audio import load_audio
+        audio = torch.from_numpy(load_audio(filename))
+    else:
+        audio = torch.as_tensor(filename, dtype=torch.float32)
+    audio = audio.to(model.device)
+    nz = torch.randn_like(audio) if noise is None else torch.as_tensor(noise, dtype=torch.float32).to(model.device)
+    audio = audio + nz * 0.001
+    prob = model.probabilities(audio, hop=TRAIN_HOP, batch_size=NET_BATCH)
+    lt, band = _viterbi_constants(prob.device)
+    bins = model.ops.viterbi_decode(prob, lt, 512, _frequency_to_bins(50.0), _frequency_to_bins(1000.0, ceil=True), band=band)
+    both = torch.stack([bins.to(torch.float32), prob.gather(1, bins.to(torch.int64)[:, None])[:, 0]])      # [2, frames]: bins < 360 are exact in fp32
+
+    def finish(dither=None, parts=False):
+        host = both.cpu()
+        pitch = bins_to_hz(host[0].to(torch.int64), dither).float().numpy()
+        f0 = f0_train_postfilter(pitch, host[1].numpy())
+        return (f0, host[0].to(torch.int64).numpy(), host[1].numpy()) if parts else f0      # parts: the decoded bins and the raw periodicity (tests)
+    return finish

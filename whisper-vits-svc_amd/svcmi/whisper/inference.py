@@ -146,3 +146,24 @@ def pred_ppg(whisper, wavPath, ppgPath, device):
     SURVEY.md 8f); writes the same float32 [T50, 1280] .npy."""
     from . import audio
     np.save(ppgPath, ppg_from_audio(whisper, audio.load_audio(wavPath)).cpu().numpy(), allow_pickle=False)
+
+
+TRAIN_SAMPLES = 30 * 16000          # whisper/audio.py N_SAMPLES: pad_or_trim's length
+
+
+@torch.no_grad()
+def pred_ppg_train(whisper, audio):
+    """prepare/preprocess_ppg.py:29-39, the TRAINING recipe: the clip padded with zeros or trimmed to 30 s (``pad_or_trim``), GPU log-mel,
+    ``encoder(mel)`` WITHOUT mel noise, rows ``[: n // 320]`` -> device tensor [min(n // 320, n_audio_ctx), state].  ``audio``: wav path, or a
+    16 kHz float waveform [n] (numpy, or a tensor on any device).  Like the reference it keeps at most the 1500 rows of one 30 s window."""
+    from . import audio as A
+    if isinstance(audio, str):
+        audio = A.load_audio(audio)
+    wav = torch.as_tensor(audio, dtype=torch.float32).to(whisper.device).reshape(-1)
+    n = wav.shape[0]
+    if n >= TRAIN_SAMPLES:
+        wav = wav[:TRAIN_SAMPLES]
+    else:
+        wav = torch.nn.functional.pad(wav, (0, TRAIN_SAMPLES - n))
+    mel = A.log_mel_spectrogram(wav, ops=whisper.ops, device=whisper.device)
+    return whisper.encoder(mel.unsqueeze(0), None)[0, :n // 320]
