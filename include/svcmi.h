@@ -447,6 +447,42 @@ int svcmi_group_mean_f32(const float* x, int32_t rows_per_group, int32_t groups,
 int svcmi_linear_spectrogram_f32(const float* x, int64_t x_bstride, int32_t batch, int64_t n, const float* basis, int32_t n_fft, int32_t hop,
                                  int32_t pad, float eps, float* out, int64_t frames, void* stream);
 
+/* Checkpoint scoring (vits_extend/validation.py, stft.py, stft_loss.py) without materialised spectrograms (csrc/spectral_loss.hip; added
+ * under ABI 22: purely additive).
+ *   stft_distance: one STFT resolution of a pair, x = the predicted and y = the recorded signal, [batch][n] fp32 with batch strides
+ *               x_bstride / y_bstride floats (>= n).  With re | im as in svcmi_linear_spectrogram_f32 (the same `basis`, pad and frames;
+ *               torch.stft's center=True is pad = n_fft / 2, frames = 1 + n / hop) and m = sqrt(max(re^2 + im^2, floor)) (stft_loss.py:28,
+ *               floor = 1e-7):   out[b][0] = sum (my - mx)^2,  out[b][1] = sum my^2,  out[b][2] = sum |log my - log mx|
+ *               over all k < bins and t < frames, as doubles.  Each table fragment feeds both signals, which go through the same
+ *               arithmetic chain: stft_distance(x, x) is exactly (0, sum, 0).  No atomics: every block of the grid (32 frames x 64 bins)
+ *               writes one fp32 triple to its own slot of `partials`, and a second kernel adds an item's slots in ascending order in
+ *               fp64.  The three doubles of an item depend on its samples and the table alone, not on the batch index, the batch size
+ *               or the stream.  `partials`: at least svcmi_stft_distance_workspace_bytes(batch, n, n_fft, hop, pad) bytes
+ *               (= 12 * batch * ceil(frames / 32) * ceil(bins / 64)), overwritten; launches that may overlap need their own.
+ *               SVCMI_EINVAL before anything is launched or written for a null pointer, batch < 1, hop < 1, pad < 0, an odd n_fft (or
+ *               < 2), n <= pad, n + 2 * pad < n_fft, another `frames`, a batch stride < n with batch > 1, floor <= 0, partials_bytes too
+ *               small; SVCMI_EALIGN for x / y / basis / partials not 4-byte or out not 8-byte aligned; SVCMI_EUNSUPPORTED for
+ *               batch > 65535.  The workspace query returns SVCMI_EINVAL (negative) for a geometry the launch would refuse.
+ *   log_mel:    out[b][m][t] = log(max(sum_{k < bins} mel[m][k] * spec[b][k][t], clip)), TacotronSTFT.mel_spectrogram after the magnitude
+ *               (stft.py:94-104, clip = 1e-5); spec [batch][bins][frames] (svcmi_linear_spectrogram_f32 with eps = 1e-9), out
+ *               [batch][n_mel][frames], both contiguous.  The filterbank comes TRANSPOSED: melT[k][m], k < bins, row stride ldm floats,
+ *               ldm >= n_mel rounded up to a multiple of 32, the columns m >= n_mel finite (zeros): a half-wave reads 32 consecutive
+ *               floats.  On the fp32 matrix cores, every output one accumulator chain over k in ascending order.  SVCMI_EINVAL for a null
+ *               pointer, batch / bins / frames / n_mel < 1, a smaller ldm, clip <= 0; SVCMI_EALIGN; SVCMI_EUNSUPPORTED for batch > 65535.
+ *   abs_diff_sum: out[b] = sum_{i < count} |a[b][i] - b[b][i]| as a double (the mel L1 before its division); batch strides in floats
+ *               (>= count).  A block sums 4096 consecutive elements in a fixed order into its own slot of `partials` (at least
+ *               svcmi_abs_diff_sum_workspace_bytes(batch, count) = 4 * batch * ceil(count / 4096) bytes); the slots are added in ascending
+ *               order in fp64.  Errors as stft_distance. */
+int64_t svcmi_stft_distance_workspace_bytes(int32_t batch, int64_t n, int32_t n_fft, int32_t hop, int32_t pad);
+int svcmi_stft_distance_f32(const float* x, int64_t x_bstride, const float* y, int64_t y_bstride, int32_t batch, int64_t n, const float* basis,
+                            int32_t n_fft, int32_t hop, int32_t pad, float floor_, int64_t frames, float* partials, int64_t partials_bytes,
+                            double* out, void* stream);
+int svcmi_log_mel_f32(const float* spec, int32_t batch, int32_t bins, int64_t frames, const float* melT, int32_t ldm, int32_t n_mel, float clip,
+                      float* out, void* stream);
+int64_t svcmi_abs_diff_sum_workspace_bytes(int32_t batch, int64_t count);
+int svcmi_abs_diff_sum_f32(const float* a, int64_t a_bstride, const float* b, int64_t b_bstride, int32_t batch, int64_t count, float* partials,
+                           int64_t partials_bytes, double* out, void* stream);
+
 /* CREPE F0 extractor glue (row N3; the six convolutions and the classifier are svcmi_conv_gemm_f32 launches):
  *   crepe_frames: crepe/core.py:664-703 -- frame f = samples [f*hop - 512, f*hop + 512) of the waveform (zeros outside
  *                 [0, n)), minus its mean, divided by max(1e-10, unbiased std).  Written as rows of `ld` (>= 1532, % 4 == 0)

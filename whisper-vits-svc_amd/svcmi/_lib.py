@@ -212,6 +212,11 @@ SIGNATURES = {
     "svcmi_logmel_finish_f32": (c_int, [_P, _P, _P, _I, _I, _I, _P]),
     "svcmi_pcm_resample_f32": (c_int, [_P, _I, _I, _L, _P, _I, _I, _I, _I, _P, _L, _P]),
     "svcmi_linear_spectrogram_f32": (c_int, [_P, _L, _I, _L, _P, _I, _I, _I, _F, _P, _L, _P]),
+    "svcmi_stft_distance_workspace_bytes": (c_int64, [_I, _L, _I, _I, _I]),
+    "svcmi_stft_distance_f32": (c_int, [_P, _L, _P, _L, _I, _L, _P, _I, _I, _I, _F, _L, _P, _L, _P, _P]),
+    "svcmi_log_mel_f32": (c_int, [_P, _I, _I, _L, _P, _I, _I, _F, _P, _P]),
+    "svcmi_abs_diff_sum_workspace_bytes": (c_int64, [_I, _L]),
+    "svcmi_abs_diff_sum_f32": (c_int, [_P, _L, _P, _L, _I, _L, _P, _L, _P, _P]),
     "svcmi_lstm_step_f32": (c_int, [_P, _L, _P, _P, _L, _I, _P, _I, _I, _I, _I, _I, _P]),
     "svcmi_preemph_pad_f32": (c_int, [_P, _P, _I, _L, _I, _F, _P]),
     "svcmi_magnitude_spectrum_f32": (c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),

@@ -680,6 +680,86 @@ class Ops:
                    self._stream(), work={"flops": 4.0 * B * frames * bins * n_fft, "bytes": 4.0 * (B * n + basis.numel() + out.numel())})
         return out
 
+    # ------------------------------------------------------------------ checkpoint scoring (csrc/spectral_loss.hip)
+    def stft_distance(self, x, y, basis, n_fft, hop, pad=None, floor=1e-7, out=None, workspace=None):
+        """One STFT resolution of a pair: ``x`` predicted, ``y`` recorded, float32 [B, n] (unit stride along n, any batch strides) ->
+        float64 [B, 3] = (sum (my - mx)^2, sum my^2, sum |log my - log mx|) over all bins x frames of the signals reflect-padded by ``pad``
+        (default n_fft // 2: torch.stft's center=True), m = sqrt(max(re^2 + im^2, floor)) (svcmi_stft_distance_f32: no spectrogram is
+        ever written).  ``basis``: the table of ``svcmi.vits.spectrogram.spectrogram_basis``.  ``workspace``: a float32 tensor of
+        ``stft_distance_workspace(...)`` elements (default: a fresh one per call, so calls on different streams never share it)."""
+        self._chk(x, y, basis, out, workspace)
+        for name, t in (("x", x), ("y", y)):
+            if not (t.dim() == 2 and t.dtype == torch.float32 and (t.shape[1] <= 1 or t.stride(1) == 1)):
+                raise SvcmiError(f"stft_distance: {name} must be float32 [B, n] with unit stride along n")
+        if x.shape != y.shape or x.device != y.device:
+            raise SvcmiError(f"stft_distance: x {tuple(x.shape)} on {x.device} and y {tuple(y.shape)} on {y.device} differ")
+        bins = n_fft // 2 + 1
+        if not (basis.dtype == torch.float32 and basis.is_contiguous() and tuple(basis.shape) == (n_fft, 2 * bins)):
+            raise SvcmiError("stft_distance: basis must be a contiguous float32 [n_fft, n_fft + 2] table")
+        B, n = x.shape
+        pad = n_fft // 2 if pad is None else pad
+        frames = 1 + (n + 2 * pad - n_fft) // hop if hop >= 1 and n + 2 * pad >= n_fft else 0
+        need = self.stft_distance_workspace(B, n, n_fft, hop, pad)
+        if workspace is None:
+            workspace = torch.empty(max(need, 1), dtype=torch.float32, device=x.device)
+        elif not (workspace.dtype == torch.float32 and workspace.is_contiguous() and workspace.numel() >= need):
+            raise SvcmiError(f"stft_distance: workspace must be a contiguous float32 tensor of at least {need} elements")
+        if out is None:
+            out = torch.empty(B, 3, dtype=torch.float64, device=x.device)
+        elif not (out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (B, 3)):
+            raise SvcmiError("stft_distance: out must be a contiguous float64 [B, 3] tensor")
+        self._call("svcmi_stft_distance_f32", _ptr(x), x.stride(0), _ptr(y), y.stride(0), B, n, _ptr(basis), n_fft, hop, pad, float(floor), frames,
+                   _ptr(workspace), 4 * workspace.numel(), _ptr(out), self._stream(),
+                   work={"flops": 8.0 * B * frames * bins * n_fft, "bytes": 4.0 * (2 * B * n + basis.numel())})
+        return out
+
+    def stft_distance_workspace(self, batch, n, n_fft, hop, pad=None):
+        """float32 elements of ``stft_distance``'s workspace (svcmi_stft_distance_workspace_bytes / 4); raises for a geometry the launch refuses."""
+        nbytes = self.lib.svcmi_stft_distance_workspace_bytes(batch, n, n_fft, hop, n_fft // 2 if pad is None else pad)
+        if nbytes < 0:
+            raise SvcmiError(f"stft_distance: batch {batch}, n {n}, n_fft {n_fft}, hop {hop}, pad {pad} is not a valid geometry (code {nbytes})")
+        return nbytes // 4
+
+    def log_mel(self, spec, melT, n_mel, clip=1e-5, out=None):
+        """spec [B, bins, frames] float32 contiguous -> log(max(mel @ spec, clip)) [B, n_mel, frames] on the matrix cores (svcmi_log_mel_f32).
+        ``melT``: the filterbank transposed and padded, contiguous float32 [bins, ldm] with ldm >= n_mel rounded up to 32 and zeros in the
+        columns past n_mel (``svcmi.vits_extend.stft.mel_table``)."""
+        self._chk(spec, melT, out)
+        if not (spec.dim() == 3 and spec.dtype == torch.float32 and spec.is_contiguous()):
+            raise SvcmiError("log_mel: spec must be a contiguous float32 [B, bins, frames] tensor")
+        B, bins, frames = spec.shape
+        if not (melT.dim() == 2 and melT.dtype == torch.float32 and melT.is_contiguous() and melT.shape[0] == bins
+                and melT.shape[1] >= (n_mel + 31) // 32 * 32):
+            raise SvcmiError("log_mel: melT must be a contiguous float32 [bins, ldm] table, ldm >= n_mel rounded up to 32")
+        if out is None:
+            out = torch.empty(B, n_mel, frames, dtype=torch.float32, device=spec.device)
+        elif not (out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, n_mel, frames)):
+            raise SvcmiError("log_mel: out must be a contiguous float32 [B, n_mel, frames] tensor")
+        self._call("svcmi_log_mel_f32", _ptr(spec), B, bins, frames, _ptr(melT), melT.shape[1], n_mel, float(clip), _ptr(out), self._stream(),
+                   work={"flops": 2.0 * B * frames * bins * n_mel, "bytes": 4.0 * (spec.numel() + melT.numel() + out.numel())})
+        return out
+
+    def abs_diff_sum(self, a, b, out=None):
+        """sum |a - b| per batch item of two equal-shaped float32 tensors [B, ...] (each item contiguous, any batch stride) -> float64 [B]
+        (svcmi_abs_diff_sum_f32: fixed-order partials, no atomics)."""
+        self._chk(a, b, out)
+        if a.shape != b.shape or a.dim() < 2 or a.dtype != torch.float32 or b.dtype != torch.float32 or a.device != b.device:
+            raise SvcmiError("abs_diff_sum: a and b must be float32 tensors [B, ...] of one shape on one device")
+        if not (a[0].is_contiguous() and b[0].is_contiguous()):
+            raise SvcmiError("abs_diff_sum: every batch item must be contiguous")
+        B, count = a.shape[0], a[0].numel()
+        nbytes = self.lib.svcmi_abs_diff_sum_workspace_bytes(B, count)
+        if nbytes < 0:
+            raise SvcmiError(f"abs_diff_sum: batch {B} x {count} elements is not a valid shape")
+        workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=a.device)
+        if out is None:
+            out = torch.empty(B, dtype=torch.float64, device=a.device)
+        elif not (out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (B,)):
+            raise SvcmiError("abs_diff_sum: out must be a contiguous float64 [B] tensor")
+        self._call("svcmi_abs_diff_sum_f32", _ptr(a), a.stride(0), _ptr(b), b.stride(0), B, count, _ptr(workspace), nbytes, _ptr(out), self._stream(),
+                   work={"bytes": 8.0 * B * count})
+        return out
+
     # ------------------------------------------------------------------ speaker encoder (csrc/lstm.hip)
     def lstm_step(self, gx, whh, hseq, c, t):
         """One time step of one LSTM layer, in place: ``gx`` [B, T, 4H] (tile order, biases included), ``whh`` [4H, H] (tile order),

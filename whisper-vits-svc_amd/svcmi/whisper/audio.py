@@ -34,8 +34,9 @@ NBINS = N_FFT // 2 + 1          # 201
 HALF = 204                      # re / im blocks of the DFT output, padded to a multiple of 4
 
 
-def slaney_mel_filterbank(sr=SAMPLE_RATE, n_fft=N_FFT, n_mels=N_MELS):
-    """librosa.filters.mel(sr, n_fft, n_mels) defaults (fmin=0, fmax=sr/2, htk=False, norm='slaney') -> float32 [n_mels, 1+n_fft/2]."""
+def slaney_mel_filterbank(sr=SAMPLE_RATE, n_fft=N_FFT, n_mels=N_MELS, fmin=0.0, fmax=None):
+    """librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax) defaults (fmin=0, fmax=sr/2, htk=False, norm='slaney') -> float32 [n_mels, 1+n_fft/2]."""
+    fmax = sr / 2.0 if fmax is None else float(fmax)
     f_sp, min_log_hz = 200.0 / 3.0, 1000.0
     min_log_mel, logstep = min_log_hz / f_sp, math.log(6.4) / 27.0
 
@@ -48,7 +49,7 @@ def slaney_mel_filterbank(sr=SAMPLE_RATE, n_fft=N_FFT, n_mels=N_MELS):
         return np.where(m >= min_log_mel, min_log_hz * np.exp(logstep * (m - min_log_mel)), f_sp * m)
 
     fftfreqs = np.linspace(0.0, sr / 2.0, 1 + n_fft // 2)
-    mel_f = mel_to_hz(np.linspace(hz_to_mel(0.0), hz_to_mel(sr / 2.0), n_mels + 2))
+    mel_f = mel_to_hz(np.linspace(hz_to_mel(float(fmin)), hz_to_mel(fmax), n_mels + 2))
     fdiff = np.diff(mel_f)
     ramps = mel_f[:, None] - fftfreqs[None, :]
     w = np.zeros((n_mels, 1 + n_fft // 2))
