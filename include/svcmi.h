@@ -634,6 +634,67 @@ int64_t svcmi_speaker_encoder_workspace_bytes(const svcmi_speaker_model* m, int3
 int svcmi_speaker_encoder_fwd(const svcmi_speaker_model* m, const float* mel, int32_t batch, int32_t t, float* emb, void* workspace,
                               int64_t workspace_bytes, void* stream);
 
+/* ---- Silero voice-activity detector (vad/utils.py, the 16 kHz model of vad/assets/silero_vad.jit; svc_inference_post.py).  Added under
+ * ABI 22: purely additive.  fp32 only.  Per window of 512 samples: reflect pad by 96 inside the window, 8 STFT frames (258 basis rows of
+ * 256 taps, hop 64), magnitude, log1p(2^20 mag) minus its smoothed mean, four ConvBlocks relu(pw(relu(dw(x))) + res(x)) (depthwise k = 5)
+ * of 258 -> 16 -> 32 -> 32 -> 64 channels, each followed by a 1x1 convolution (stride 2, 2, 2, 1) + BatchNorm + ReLU: one 64-vector;
+ * then ONE step of a 2-layer LSTM(64, 64) (gate order i, f, g, o) whose state runs from window to window, and
+ * p = sigmoid(dec_w . relu(h of layer 1) + dec_b). */
+typedef struct svcmi_vad_conv_block {
+    const float *dw_w, *dw_b;                       /* depthwise [c_in][5], [c_in] */
+    const float *pw_w, *pw_b;                       /* pointwise [c_out][c_in], [c_out] */
+    const float *proj_w, *proj_b;                   /* residual 1x1 [c_out][c_in], [c_out]; both NULL = identity (c_in == c_out) */
+    int32_t c_in, c_out;
+} svcmi_vad_conv_block;
+typedef struct svcmi_vad_down {
+    const float *w, *b;                             /* 1x1 convolution [c][c], [c] */
+    const float *scale, *shift;                     /* BatchNorm in eval mode: scale = weight / sqrt(running_var + eps), shift = bias - running_mean * scale */
+    int32_t c, stride;
+} svcmi_vad_down;
+typedef struct svcmi_vad_model {
+    const float* basis_t;                           /* the STFT basis TRANSPOSED: [256 taps][260], column r < 258 = basis row r */
+    const float* filt;                              /* the normaliser's 7 smoothing taps */
+    svcmi_vad_conv_block block[4];                  /* 258 -> 16, 16 -> 32, 32 -> 32, 32 -> 64 */
+    svcmi_vad_down down[4];                         /* strides 2, 2, 2, 1 */
+    const float *gate0_w, *gate0_b;                 /* W_ih of LSTM layer 0 [256][64] and b_ih + b_hh [256] */
+    const float *whh0_t, *wih1_t, *whh1_t;          /* W_hh0, W_ih1, W_hh1 TRANSPOSED: [64][256] (element [k][j] = row j, column k) */
+    const float* gate1_b;                           /* b_ih + b_hh of layer 1 [256] */
+    const float* dec_w;                             /* [64] */
+    float dec_b;
+    int32_t reserved;
+} svcmi_vad_model;
+int64_t svcmi_vad_model_bytes(void);                /* sizeof(svcmi_vad_model), for a binding's layout check */
+
+/* The three kernels (csrc/vad.hip).  Recordings: `batch` mono 16 kHz signals inside one buffer, recording b = audio[offsets[b] ..
+ * offsets[b] + lengths[b]); offsets / lengths are DEVICE arrays of int64.  Recording b has W_b = min(wmax, ceil(lengths[b] / 512))
+ * windows, the last one zero-padded on the right.  feat [batch][wmax][64], gates [batch][wmax][256], probs [batch][wmax]: rows
+ * w >= W_b are not written.
+ *   vad_frontend:  everything in front of the LSTM, one block per window: feat = the 64-vector, gates = W_ih0 feat + b_ih0 + b_hh0.
+ *                  Every sum is one chain in ascending index order, no atomics: a window's bits depend on its 512 samples and the
+ *                  weights alone, not on the run, on wmax or on the batch.
+ *   vad_lstm_scan: both LSTM layers and the decoder over a recording's W_b windows, one block per recording (recordings of different
+ *                  lengths each scan their own W_b; no block waits for another).  state: NULL = start from zero; else
+ *                  [batch][4][64] = h0, c0, h1, c1, read at the start and overwritten with the state after the last window.
+ *                  Saturated gates give exactly 0 / 1, never NaN.
+ *   mask_spans:    out[i] = in[i] if some span s has spans[s][0] * ratio <= i < spans[s][1] * ratio, else 0, for
+ *                  i < n_out = min(n_in, ratio * n_ref) (svc_inference_post.py:39-49 with ratio = 2).  spans: device int32
+ *                  [n_spans][2], sorted and disjoint; n_spans = 0 (spans may be NULL) zeroes everything.
+ * SVCMI_EINVAL before anything is launched for a null pointer (model members included), batch < 1, wmax < 1, n_in / n_ref / ratio < 1,
+ * n_spans < 0, another n_out; SVCMI_EUNSUPPORTED for channel counts or strides other than the architecture above, batch > 65535;
+ * SVCMI_EALIGN for a pointer that is not aligned to its element. */
+int svcmi_vad_frontend_f32(const svcmi_vad_model* m, const float* audio, const int64_t* offsets, const int64_t* lengths, int32_t batch,
+                           int32_t wmax, float* feat, float* gates, void* stream);
+int svcmi_vad_lstm_scan_f32(const svcmi_vad_model* m, const float* gates, const int64_t* lengths, int32_t batch, int32_t wmax, float* state,
+                            float* probs, void* stream);
+int svcmi_mask_spans_f32(const float* in, int64_t n_in, const int32_t* spans, int32_t n_spans, int64_t n_ref, int32_t ratio, float* out,
+                         int64_t n_out, void* stream);
+/* The two launches on one workspace: probs [batch][wmax] (rows w >= W_b not written).  The workspace holds feat and gates:
+ * svcmi_vad_workspace_bytes(batch, wmax) = 1280 * batch * wmax + 256 bytes (SVCMI_EINVAL for batch or wmax < 1).  SVCMI_EINVAL also for a
+ * workspace that is too small or not 256-byte aligned. */
+int64_t svcmi_vad_workspace_bytes(int32_t batch, int32_t wmax);
+int svcmi_vad_probs_fwd(const svcmi_vad_model* m, const float* audio, const int64_t* offsets, const int64_t* lengths, int32_t batch,
+                        int32_t wmax, float* state, float* probs, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- SynthesizerInfer (vits/models.py:211-256) */
 /* layer classes of the per-layer mixed-precision policy: prior encoder (enc_p: pre / hub / attention + FFN layers / proj, and its attention
  * kernel), flow (pre / in / res_skip / post of every coupling layer), the generator's trunk (conv_pre + every ups[i]), and the AMP-block

@@ -26,7 +26,7 @@ enum Op {
     OP_CONV_F32, OP_CONV_LP, OP_CONV_GROUP_F32, OP_CONV_GROUP_LP, OP_LAYERNORM, OP_SPLITK_LN, OP_ATTENTION, OP_SNAKE_ALIAS,
     OP_SNAKE_ALIAS_GROUP, OP_BLOCK_MEAN, OP_SNAKE_CONV, OP_SNAKE_CONV_GROUP, OP_UPSAMPLE_NOISE, OP_SNAKE_POST, OP_WN_GATE,
     OP_COUPLING_PRE, OP_COUPLING_POST, OP_EMBED_PITCH, OP_SAMPLE_PRIOR, OP_NCL_TO_NLC, OP_COPY2D, OP_PITCH_PREFIX, OP_PITCH_SOURCE,
-    OP_ATTENTION16, OP_SNAKE_CONV_GROUP_LP, OP_LSTM_STEP, OP_L2NORM_ROWS, OP_COUNT
+    OP_ATTENTION16, OP_SNAKE_CONV_GROUP_LP, OP_LSTM_STEP, OP_L2NORM_ROWS, OP_VAD_FRONTEND, OP_VAD_LSTM_SCAN, OP_COUNT
 };
 const char* const OP_NAMES[OP_COUNT] = {
     "svcmi_conv_gemm_f32", "svcmi_conv_gemm_lp", "svcmi_conv_gemm_group_f32", "svcmi_conv_gemm_group_lp", "svcmi_layernorm_f32",
@@ -34,7 +34,7 @@ const char* const OP_NAMES[OP_COUNT] = {
     "svcmi_snake_conv_f32", "svcmi_snake_conv_group_f32", "svcmi_upsample_noise_f32", "svcmi_snake_post_f32", "svcmi_wn_gate_f32",
     "svcmi_coupling_pre_f32", "svcmi_coupling_post_f32", "svcmi_embed_pitch_f32", "svcmi_sample_prior_f32", "svcmi_ncl_to_nlc_f32",
     "svcmi_copy2d_f32", "svcmi_pitch_prefix_f64", "svcmi_pitch_source_f32", "svcmi_attention16", "svcmi_snake_conv_group_lp",
-    "svcmi_lstm_step_f32", "svcmi_l2norm_rows_f32"};
+    "svcmi_lstm_step_f32", "svcmi_l2norm_rows_f32", "svcmi_vad_frontend_f32", "svcmi_vad_lstm_scan_f32"};
 
 // ------------------------------------------------------------------------------------------------ per-launch trace (bench.py)
 struct TraceRec {
@@ -901,6 +901,24 @@ void speaker_fwd(Ctx& c, const svcmi_speaker_model& m, const float* mel, int B, 
     run(c, OP_L2NORM_ROWS, 0.0, 8.0 * B * P, [&] { return svcmi_l2norm_rows_f32(last, P, B, P, emb, P, c.stream); });
 }
 
+// ------------------------------------------------------------------------------------------------ voice-activity detector
+// vad/utils.py: the probabilities of every window of `batch` recordings in two launches (csrc/vad.hip): the convolutional part of all
+// windows at once, then one serial scan per recording.  Per window: 2 * (258 * 8 * 256 + 2 * 258 * 16 * 8 + ...) ~ 1.3 MFLOP in front of
+// the LSTM, 2 * 3 * 256 * 64 in it.
+void vad_fwd(Ctx& c, const svcmi_vad_model& m, const float* audio, const int64_t* offsets, const int64_t* lengths, int B, int W, float* state,
+             float* probs) {
+    if (B < 1 || W < 1) { c.rc = SVCMI_EINVAL; return; }
+    float* feat = c.ar.f((int64_t)B * W * 64);
+    float* gates = c.ar.f((int64_t)B * W * 256);
+    const double n = (double)B * W;
+    run(c, OP_VAD_FRONTEND, 1.3e6 * n, 4.0 * n * (512 + 64 + 256), [&] {
+        return svcmi_vad_frontend_f32(&m, audio, offsets, lengths, B, W, feat, gates, c.stream);
+    });
+    run(c, OP_VAD_LSTM_SCAN, 2.0 * 3 * 256 * 64 * n, 4.0 * n * 257, [&] {
+        return svcmi_vad_lstm_scan_f32(&m, gates, lengths, B, W, state, probs, c.stream);
+    });
+}
+
 Ctx make_ctx(void* ws, int64_t bytes, void* stream, bool plan) {
     Ctx c;
     c.stream = stream;
@@ -943,6 +961,23 @@ extern "C" int svcmi_speaker_encoder_fwd(const svcmi_speaker_model* m, const flo
     if (((uintptr_t)mel & 15) || ((uintptr_t)emb & 3)) return SVCMI_EALIGN;
     Ctx c = make_ctx(workspace, workspace_bytes, stream, false);
     speaker_fwd(c, *m, mel, batch, t, emb);
+    return finish(c);
+}
+
+extern "C" int64_t svcmi_vad_workspace_bytes(int32_t batch, int32_t wmax) {
+    Ctx c = make_ctx(nullptr, 0, nullptr, true);
+    svcmi_vad_model m;
+    memset(&m, 0, sizeof(m));
+    vad_fwd(c, m, nullptr, nullptr, nullptr, batch, wmax, nullptr, nullptr);
+    return c.rc ? (int64_t)c.rc : c.ar.peak + 256;
+}
+
+extern "C" int svcmi_vad_probs_fwd(const svcmi_vad_model* m, const float* audio, const int64_t* offsets, const int64_t* lengths, int32_t batch,
+                                   int32_t wmax, float* state, float* probs, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!m || !audio || !offsets || !lengths || !probs || !workspace || batch < 1 || wmax < 1) return SVCMI_EINVAL;
+    if (((uintptr_t)workspace & 255) || workspace_bytes < svcmi_vad_workspace_bytes(batch, wmax)) return SVCMI_EINVAL;
+    Ctx c = make_ctx(workspace, workspace_bytes, stream, false);
+    vad_fwd(c, *m, audio, offsets, lengths, batch, wmax, state, probs);
     return finish(c);
 }
 

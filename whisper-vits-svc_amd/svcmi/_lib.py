@@ -172,6 +172,24 @@ class SpeakerModel(Structure):
                 ("layers", LstmLayer * MAX_LSTM_LAYERS)]
 
 
+class VadConvBlock(Structure):
+    """svcmi_vad_conv_block"""
+    _fields_ = [("dw_w", c_void_p), ("dw_b", c_void_p), ("pw_w", c_void_p), ("pw_b", c_void_p), ("proj_w", c_void_p), ("proj_b", c_void_p),
+                ("c_in", c_int32), ("c_out", c_int32)]
+
+
+class VadDown(Structure):
+    """svcmi_vad_down"""
+    _fields_ = [("w", c_void_p), ("b", c_void_p), ("scale", c_void_p), ("shift", c_void_p), ("c", c_int32), ("stride", c_int32)]
+
+
+class VadModel(Structure):
+    """svcmi_vad_model"""
+    _fields_ = [("basis_t", c_void_p), ("filt", c_void_p), ("block", VadConvBlock * 4), ("down", VadDown * 4),
+                ("gate0_w", c_void_p), ("gate0_b", c_void_p), ("whh0_t", c_void_p), ("wih1_t", c_void_p), ("whh1_t", c_void_p),
+                ("gate1_b", c_void_p), ("dec_w", c_void_p), ("dec_b", c_float), ("reserved", c_int32)]
+
+
 class TraceRecord(Structure):
     _fields_ = [("op", c_int32), ("ms", c_float), ("flops", c_double), ("bytes", c_double)]
 
@@ -225,6 +243,12 @@ SIGNATURES = {
     "svcmi_group_mean_f32": (c_int, [_P, _I, _I, _I, _P, _P]),
     "svcmi_speaker_encoder_workspace_bytes": (c_int64, [POINTER(SpeakerModel), _I, _I]),
     "svcmi_speaker_encoder_fwd": (c_int, [POINTER(SpeakerModel), _P, _I, _I, _P, _P, _L, _P]),
+    "svcmi_vad_model_bytes": (c_int64, []),
+    "svcmi_vad_frontend_f32": (c_int, [POINTER(VadModel), _P, _P, _P, _I, _I, _P, _P, _P]),
+    "svcmi_vad_lstm_scan_f32": (c_int, [POINTER(VadModel), _P, _P, _I, _I, _P, _P, _P]),
+    "svcmi_mask_spans_f32": (c_int, [_P, _L, _P, _I, _L, _I, _P, _L, _P]),
+    "svcmi_vad_workspace_bytes": (c_int64, [_I, _I]),
+    "svcmi_vad_probs_fwd": (c_int, [POINTER(VadModel), _P, _P, _P, _I, _I, _P, _P, _P, _L, _P]),
     "svcmi_crepe_frames_f32": (c_int, [_P, _L, _I, _I, _I, _P, _I, _P]),
     "svcmi_bn_maxpool2_f32": (c_int, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _I, _I, _P]),
     "svcmi_viterbi_decode": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
@@ -286,4 +310,6 @@ def load_library(path=None):
     mine = [_c.sizeof(t) for t in (Weight, WhisperModel, SynthModel, SynthIO, TraceRecord, ConvDesc, SnakeConvDesc)]
     if list(sizes[:n]) != mine:
         raise SvcmiError(f"struct layout mismatch: library {list(sizes[:n])} vs binding {mine}")
+    if lib.svcmi_vad_model_bytes() != _c.sizeof(VadModel):
+        raise SvcmiError(f"struct layout mismatch: svcmi_vad_model is {lib.svcmi_vad_model_bytes()} bytes in the library, {_c.sizeof(VadModel)} in the binding")
     return lib

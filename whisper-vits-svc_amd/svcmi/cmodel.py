@@ -142,3 +142,23 @@ def synth_cmodel(w, ops, prec=PREC_F32):
                 b.a1_alpha[q], b.a1_beta[q] = blk["a1"][q][0].data_ptr(), blk["a1"][q][1].data_ptr()
                 b.a2_alpha[q], b.a2_beta[q] = blk["a2"][q][0].data_ptr(), blk["a2"][q][1].data_ptr()
     return CModel(m, keep)
+
+
+def vad_cmodel(w):
+    """``w``: svcmi.weights.VadWeights.  fp32 only."""
+    m, keep = _lib.VadModel(), [w]
+    m.basis_t, m.filt = w.basis_t.data_ptr(), w.filt.data_ptr()
+    for i, blk in enumerate(w.blocks):
+        b = m.block[i]
+        b.c_in, b.c_out = blk["c_in"], blk["c_out"]
+        for k in ("dw_w", "dw_b", "pw_w", "pw_b", "proj_w", "proj_b"):
+            setattr(b, k, 0 if blk[k] is None else blk[k].data_ptr())
+    for i, dn in enumerate(w.downs):
+        d = m.down[i]
+        d.c, d.stride = dn["c"], dn["stride"]
+        for k in ("w", "b", "scale", "shift"):
+            setattr(d, k, dn[k].data_ptr())
+    for k in ("gate0_w", "gate0_b", "whh0_t", "wih1_t", "whh1_t", "gate1_b", "dec_w"):
+        setattr(m, k, getattr(w, k).data_ptr())
+    m.dec_b = w.dec_b
+    return CModel(m, keep)

@@ -822,6 +822,72 @@ class Ops:
         self._stage_call("svcmi_speaker_encoder_fwd", ctypes.byref(m), _ptr(mel), B, T, _ptr(out), ws, ws_bytes, self._stream())
         return out
 
+    # ------------------------------------------------------------------ voice-activity detector (csrc/vad.hip)
+    @staticmethod
+    def _vad_geometry(audio, offsets, lengths):
+        if audio.dim() != 1 or audio.dtype != torch.float32 or not audio.is_contiguous():
+            raise SvcmiError("vad: audio must be one contiguous float32 buffer [n] holding every recording")
+        for t in (offsets, lengths):
+            if t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous() or t.device != audio.device or t.shape != offsets.shape:
+                raise SvcmiError("vad: offsets / lengths must be contiguous int64 [batch] tensors on the audio's device")
+        return int(offsets.shape[0])
+
+    def vad_frontend(self, cm, audio, offsets, lengths, wmax):
+        """Everything in front of the LSTM for every window of ``batch`` recordings (recording b = audio[offsets[b] : offsets[b] +
+        lengths[b]], device int64 tensors): (feat [batch, wmax, 64], gates [batch, wmax, 256]); rows past a recording's last window
+        stay zero."""
+        self._chk(audio, offsets, lengths)
+        B = self._vad_geometry(audio, offsets, lengths)
+        feat = torch.zeros(B, wmax, 64, dtype=torch.float32, device=audio.device)
+        gates = torch.zeros(B, wmax, 256, dtype=torch.float32, device=audio.device)
+        self._call("svcmi_vad_frontend_f32", ctypes.byref(cm.struct), _ptr(audio), _ptr(offsets), _ptr(lengths), B, wmax, _ptr(feat), _ptr(gates),
+                   self._stream(), work={"flops": 1.3e6 * B * wmax})
+        return feat, gates
+
+    def vad_lstm_scan(self, cm, gates, lengths, state=None):
+        """The two LSTM layers and the decoder over every recording's windows: gates [batch, wmax, 256] (layer 0's pre-activations),
+        lengths int64 [batch] in samples -> probabilities [batch, wmax] (zero past a recording's last window).  ``state`` [batch, 4, 64]
+        (h0, c0, h1, c1) is read at the start and overwritten with the final state; None starts from zero."""
+        self._chk(gates, lengths, state)
+        B, wmax, _ = gates.shape
+        if not gates.is_contiguous() or gates.shape[2] != 256 or tuple(lengths.shape) != (B,) or lengths.dtype != torch.int64:
+            raise SvcmiError("vad_lstm_scan: gates must be contiguous [batch, wmax, 256] and lengths int64 [batch]")
+        if state is not None and not (state.is_contiguous() and tuple(state.shape) == (B, 4, 64) and state.dtype == torch.float32):
+            raise SvcmiError("vad_lstm_scan: state must be a contiguous float32 [batch, 4, 64] tensor")
+        probs = torch.zeros(B, wmax, dtype=torch.float32, device=gates.device)
+        self._call("svcmi_vad_lstm_scan_f32", ctypes.byref(cm.struct), _ptr(gates), _ptr(lengths), B, wmax, _ptr(state), _ptr(probs), self._stream())
+        return probs
+
+    def vad_probs_fwd(self, cm, audio, offsets, lengths, wmax, state=None):
+        """Both launches as ONE stage call (svcmi_vad_probs_fwd): probabilities [batch, wmax]."""
+        self._chk(audio, offsets, lengths, state)
+        B = self._vad_geometry(audio, offsets, lengths)
+        if state is not None and not (state.is_contiguous() and tuple(state.shape) == (B, 4, 64) and state.dtype == torch.float32):
+            raise SvcmiError("vad_probs_fwd: state must be a contiguous float32 [batch, 4, 64] tensor")
+        need = self.lib.svcmi_vad_workspace_bytes(B, wmax)
+        if need < 0:
+            raise SvcmiError(f"svcmi_vad_workspace_bytes failed with code {need}")
+        ws, ws_bytes = self.stage_workspace(need, audio.device)
+        probs = torch.zeros(B, wmax, dtype=torch.float32, device=audio.device)
+        self._stage_call("svcmi_vad_probs_fwd", ctypes.byref(cm.struct), _ptr(audio), _ptr(offsets), _ptr(lengths), B, wmax, _ptr(state),
+                         _ptr(probs), ws, ws_bytes, self._stream())
+        return probs
+
+    def mask_spans(self, x, spans, n_ref, ratio=2):
+        """x float32 [n_in]; spans int32 [S, 2] (sorted, disjoint, in samples of the reference rate; S may be 0) -> float32
+        [min(n_in, ratio * n_ref)]: x inside the spans scaled by ``ratio``, zero outside."""
+        self._chk(x, spans)
+        if x.dim() != 1 or x.dtype != torch.float32 or not x.is_contiguous():
+            raise SvcmiError("mask_spans: x must be a contiguous float32 [n] tensor")
+        if spans.dtype != torch.int32 or spans.dim() != 2 or spans.shape[1] != 2 or not spans.is_contiguous():
+            raise SvcmiError("mask_spans: spans must be a contiguous int32 [S, 2] tensor")
+        n = min(int(x.shape[0]), int(ratio) * int(n_ref))
+        out = torch.empty(max(n, 0), dtype=torch.float32, device=x.device)
+        S = int(spans.shape[0])
+        self._call("svcmi_mask_spans_f32", _ptr(x), x.shape[0], _ptr(spans) if S else 0, S, int(n_ref), int(ratio), _ptr(out), n, self._stream(),
+                   work={"bytes": 8.0 * n})
+        return out
+
     # ------------------------------------------------------------------ CREPE glue
     def crepe_frames(self, audio, hop, frame0, frames, ld=1536):
         """audio [n] -> normalised, first-layer-padded frames [frames, ld] (crepe/core.py:664-703)."""

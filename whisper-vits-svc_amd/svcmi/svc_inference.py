@@ -218,6 +218,7 @@ def main(args):
     from .vits.models import SynthesizerInfer
     from .whisper import inference as whisper_inf
     device = "cuda"
+    audio = None
     f0_prec = None if getattr(args, "f0_precision", "f32") == "f32" else getattr(args, "f0_precision", "f32")
     prec = None if getattr(args, "precision", "f32") == "f32" else args.precision
 
@@ -263,7 +264,19 @@ def main(args):
     vec = torch.FloatTensor(np.repeat(np.load(args.vec), 2, 0))
     print("pitch shift: ", args.shift)
     pit = torch.FloatTensor(shift_pitch(pitch_inf.load_csv_pitch(args.pit), args.shift))
-    out_audio = svc_infer(model, retrieval, spk, pit, ppg, vec, hp, device)
+    vad_post = getattr(args, "vad_post", None)
+    if not vad_post:
+        out_audio = svc_infer(model, retrieval, spk, pit, ppg, vec, hp, device)
+    else:
+        # svc_inference_post.py as a tail of the conversion: the waveform is still on the device, the 16 kHz input is the one the
+        # extractors read (loaded now if the features came from files)
+        from .svc_inference_post import SVC_RATE, apply_vad_post
+        from .vad.utils import init_jit_model
+        from .whisper.audio import load_audio
+        if int(hp.data.sampling_rate) != SVC_RATE:
+            raise ValueError(f"--vad-post masks a {SVC_RATE} Hz waveform (two samples per 16 kHz input sample); this model's rate is {hp.data.sampling_rate}")
+        wave = svc_infer(model, retrieval, spk, pit, ppg, vec, hp, device, return_tensor=True)
+        out_audio = apply_vad_post(audio if audio is not None else load_audio(args.wave), wave, init_jit_model(vad_post, device)).cpu().numpy()
     write("svc_out.wav", hp.data.sampling_rate, out_audio)
     return out_audio
 
@@ -291,6 +304,9 @@ def build_parser():
     p.add_argument("--hubert", type=str, default=os.path.join("hubert_pretrain", "hubert-soft-0d54a1f4.pt"))
     p.add_argument("--crepe", type=str, default=os.path.join("crepe", "assets", "full.pth"))
     p.add_argument("--debug", action="store_true")
+    p.add_argument("--vad-post", type=str, default=None, metavar="PATH",
+                   help="path of the Silero VAD archive (vad/assets/silero_vad.jit): zero the converted waveform wherever the input has no "
+                        "voice, as svc_inference_post.py does, before svc_out.wav is written (off by default)")
     p.add_argument("--loader", default="host", choices=["host", "gpu"],
                    help="where the input wav is decoded, downmixed and resampled to 16 kHz: host = numpy + scipy's polyphase resampler "
                         "(default); gpu = the file's PCM uploaded once and one kernel launch (the same filter, equal to fp32 rounding), "

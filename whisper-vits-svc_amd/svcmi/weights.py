@@ -322,3 +322,59 @@ class SpeakerWeights:
         for d in (self.input_dim, self.lstm_dim, self.proj_dim):
             if d % 4:
                 raise ValueError(f"speaker encoder dimension {d} is not a multiple of 4")
+
+
+VAD_BLOCKS = (("first_layer.0", 258, 16), ("encoder.3.0", 16, 32), ("encoder.7.0", 32, 32), ("encoder.11.0", 32, 64))
+VAD_DOWNS = (("encoder.0", "encoder.1", 16, 2), ("encoder.4", "encoder.5", 32, 2), ("encoder.8", "encoder.9", 32, 2), ("encoder.12", "encoder.13", 64, 1))
+VAD_HIDDEN = 64
+VAD_BASIS_LD = 260      # row stride of the transposed STFT basis (csrc/vad.hip LDB)
+
+
+class VadWeights:
+    """The 16 kHz Silero VAD model's parameters (``state_dict`` names of vad/assets/silero_vad.jit without the ``_model.`` prefix) as
+    csrc/vad.hip reads them, on one device:
+      * ``basis_t`` [256, 260]: ``feature_extractor.forward_basis_buffer`` [258, 1, 256] transposed (a wave reads 64 consecutive rows of a tap);
+      * per ConvBlock ``dw_w`` [c_in, 5], ``pw_w`` [c_out, c_in], ``proj_w`` [c_out, c_in] or None (identity residual), and the biases;
+      * per strided 1x1 convolution ``w`` [c, c], ``b``, and its BatchNorm (eval, eps 1e-5) as ``scale`` = weight / sqrt(var + eps),
+        ``shift`` = bias - mean * scale (the convolution's own weights are left alone);
+      * the LSTM: ``gate0_w`` = W_ih0 [256, 64] and ``gate0_b`` = b_ih0 + b_hh0 for the front-end kernel; ``whh0_t`` / ``wih1_t`` / ``whh1_t``
+        [64, 256] transposed for the scan kernel (thread j loads column j), ``gate1_b`` = b_ih1 + b_hh1; ``dec_w`` [64], ``dec_b``.
+    A missing key raises KeyError, a tensor of another shape ValueError."""
+
+    def __init__(self, sd, device):
+        def get(name, shape):
+            t = sd[name]
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"Silero VAD state dict: {name} has shape {tuple(t.shape)}, the 16 kHz model has {tuple(shape)}")
+            return t.detach().float()
+        f = lambda t: t.to(device).contiguous()
+        H, G = VAD_HIDDEN, 4 * VAD_HIDDEN
+        basis = get("feature_extractor.forward_basis_buffer", (258, 1, 256))[:, 0]
+        bt = torch.zeros(256, VAD_BASIS_LD)
+        bt[:, :258] = basis.t()
+        self.basis_t = f(bt)
+        self.filt = f(get("adaptive_normalization.filter_", (1, 1, 7)).reshape(7))
+        self.blocks = []
+        for name, cin, cout in VAD_BLOCKS:
+            blk = dict(c_in=cin, c_out=cout,
+                       dw_w=f(get(f"{name}.dw_conv.0.weight", (cin, 1, 5))[:, 0]), dw_b=f(get(f"{name}.dw_conv.0.bias", (cin,))),
+                       pw_w=f(get(f"{name}.pw_conv.0.weight", (cout, cin, 1))[:, :, 0]), pw_b=f(get(f"{name}.pw_conv.0.bias", (cout,))),
+                       proj_w=None, proj_b=None)
+            if cin != cout:
+                blk.update(proj_w=f(get(f"{name}.proj.weight", (cout, cin, 1))[:, :, 0]), proj_b=f(get(f"{name}.proj.bias", (cout,))))
+            self.blocks.append(blk)
+        self.downs = []
+        for conv, bn, c, stride in VAD_DOWNS:
+            scale = get(f"{bn}.weight", (c,)) / torch.sqrt(get(f"{bn}.running_var", (c,)) + 1e-5)
+            shift = get(f"{bn}.bias", (c,)) - get(f"{bn}.running_mean", (c,)) * scale
+            self.downs.append(dict(c=c, stride=stride, w=f(get(f"{conv}.weight", (c, c, 1))[:, :, 0]), b=f(get(f"{conv}.bias", (c,))),
+                                   scale=f(scale), shift=f(shift)))
+        r = "decoder.rnn."
+        self.gate0_w = f(get(r + "weight_ih_l0", (G, H)))
+        self.gate0_b = f(get(r + "bias_ih_l0", (G,)) + get(r + "bias_hh_l0", (G,)))
+        self.whh0_t = f(get(r + "weight_hh_l0", (G, H)).t())
+        self.wih1_t = f(get(r + "weight_ih_l1", (G, H)).t())
+        self.whh1_t = f(get(r + "weight_hh_l1", (G, H)).t())
+        self.gate1_b = f(get(r + "bias_ih_l1", (G,)) + get(r + "bias_hh_l1", (G,)))
+        self.dec_w = f(get("decoder.decoder.1.weight", (1, H, 1)).reshape(H))
+        self.dec_b = float(get("decoder.decoder.1.bias", (1,))[0])
