@@ -695,6 +695,53 @@ int64_t svcmi_vad_workspace_bytes(int32_t batch, int32_t wmax);
 int svcmi_vad_probs_fwd(const svcmi_vad_model* m, const float* audio, const int64_t* offsets, const int64_t* lengths, int32_t batch,
                         int32_t wmax, float* state, float* probs, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Salience F0 extractor (pitch/inference.py:31-44 compute_f0_salience -> pitch/core/salience.py).  Added under ABI 22: purely
+ * additive.  fp32 / fp64 only.  A centred STFT (zero padding, window folded into the table) restricted to the bins whose
+ * instantaneous frequency can fall into [f_min, f_max); per frame the heterodyned phase increment gives every bin an instantaneous
+ * frequency, its power |X|^2 is added into the log-frequency bin floor(bins_per_octave log2(f / f_min) + 0.5) (ascending STFT bin per
+ * log-frequency bin: a fixed order, no floating-point atomics), the column is smoothed along frequency, thresholded against the
+ * global maximum, summed over harmonics and thresholded again; then ONE dynamic programme over the whole clip in fp64.
+ * The plan is made by the host (svcmi/pitch/core/salience.py salience_plan); every pointer is a DEVICE pointer. */
+typedef struct svcmi_salience_plan {
+    const float* basis;                             /* [n_fft][2 n_bins]: column 2j = w[i] cos(2 pi (k_lo + j) i / n_fft), 2j + 1 = -w[i] sin(..), made in float64 */
+    const float* smooth;                            /* the smoothing taps [smooth_len] (symmetric, odd length) */
+    const int32_t* harm_off;                        /* harmonic summation, sparse: z[b] = sum_m harm_w[m] lf[b + harm_off[m]], m ascending */
+    const float* harm_w;                            /* [n_harm] */
+    int32_t n_fft, hop, k_lo, n_bins;               /* STFT bins k_lo .. k_lo + n_bins - 1 of n_fft / 2 + 1 */
+    int32_t n_pitch, smooth_len, n_harm, tol;       /* B log-frequency bins; |i - j| <= tol is the cheap transition */
+    float fs, f_min, f_max, bins_per_octave;        /* 1200 / R */
+    double thresh;                                  /* 10^(gamma / 20): a cell stays iff v / max + 2^-23 < thresh (a NaN quotient, max = 0, zeroes it) */
+    double log_hi, log_lo;                          /* log(score_high + 2^-23), log(score_low + 2^-23) */
+} svcmi_salience_plan;
+int64_t svcmi_salience_plan_bytes(void);            /* sizeof(svcmi_salience_plan), for a binding's layout check */
+#define SVCMI_SALIENCE_MAX_BINS 1024                /* n_bins, n_pitch and tol may not exceed this */
+
+/* The kernels (csrc/salience.hip).  frames = 1 + n / hop throughout, at least 2 (the phase increment needs a neighbour).
+ *   salience_stft: X [frames][n_bins] complex64 (re, im interleaved) of x zero-padded by n_fft / 2 on both sides (index arithmetic on the
+ *                  load).  On the fp32 matrix cores, every output one accumulator chain over the taps in ascending order: the bits
+ *                  depend on the frame's n_fft padded samples and the table alone, not on the tile, the frame count or the stream.
+ *   salience_map:  X -> lf [frames][n_pitch] (the smoothed, thresholded log-frequency spectrogram) and z [frames][n_pitch] (the
+ *                  salience map), both time-major.  gmax: two 32-bit words of scratch; afterwards the bit patterns of max(lf) and
+ *                  max(z) BEFORE thresholding (integer atomic max on non-negative floats: order-independent).  Frame 0 takes frame
+ *                  1's instantaneous frequencies.  An all-zero X gives all-zero maps, no NaN.
+ *   salience_dp:   z [frames][n_pitch] -> path int32 [frames]: D[b, 0] = log(z[0][b] + 2^-23), D[b, t] = max_j(T[b, j] + D[j, t - 1]) +
+ *                  log(z[t][b] + 2^-23) with T = log_hi for |b - j| <= tol, else log_lo, in fp64; every predecessor is evaluated, the
+ *                  lowest index wins a tie (numpy's argmax).  One block per clip.  ptr: int16 [frames][n_pitch] scratch.
+ * SVCMI_EINVAL before anything is launched for a null pointer (plan members included), frames < 2 or != 1 + n / hop, n < 1, hop < 1, an odd
+ * n_fft (or < 2), a bin range outside 0 .. n_fft / 2, n_pitch / n_harm < 1, an even smooth_len, tol < 0; SVCMI_EUNSUPPORTED for n_bins,
+ * n_pitch or tol above SVCMI_SALIENCE_MAX_BINS, smooth_len > 65, frames >= 2^31 / n_pitch; SVCMI_EALIGN for a pointer that is not aligned to
+ * its element (X: 8 bytes). */
+int svcmi_salience_stft_f32(const svcmi_salience_plan* p, const float* x, int64_t n, float* X, int64_t frames, void* stream);
+int svcmi_salience_map_f32(const svcmi_salience_plan* p, const float* X, int64_t frames, float* lf, float* z, uint32_t* gmax, void* stream);
+int svcmi_salience_dp_f64(const float* z, int64_t frames, int32_t n_pitch, int32_t tol, double log_hi, double log_lo, int16_t* ptr,
+                          int32_t* path, void* stream);
+/* waveform -> path as ONE stage call on one workspace (X, lf, the back pointers, gmax; z too when the caller passes NULL for it).
+ * SVCMI_EINVAL also for a workspace that is too small or not 256-byte aligned; the query returns a negative code for a geometry the
+ * stage would refuse. */
+int64_t svcmi_salience_workspace_bytes(const svcmi_salience_plan* p, int64_t n);
+int svcmi_salience_f0_fwd(const svcmi_salience_plan* p, const float* x, int64_t n, int32_t* path, float* z, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
 /* ---- SynthesizerInfer (vits/models.py:211-256) */
 /* layer classes of the per-layer mixed-precision policy: prior encoder (enc_p: pre / hub / attention + FFN layers / proj, and its attention
  * kernel), flow (pre / in / res_skip / post of every coupling layer), the generator's trunk (conv_pre + every ups[i]), and the AMP-block

@@ -26,7 +26,8 @@ enum Op {
     OP_CONV_F32, OP_CONV_LP, OP_CONV_GROUP_F32, OP_CONV_GROUP_LP, OP_LAYERNORM, OP_SPLITK_LN, OP_ATTENTION, OP_SNAKE_ALIAS,
     OP_SNAKE_ALIAS_GROUP, OP_BLOCK_MEAN, OP_SNAKE_CONV, OP_SNAKE_CONV_GROUP, OP_UPSAMPLE_NOISE, OP_SNAKE_POST, OP_WN_GATE,
     OP_COUPLING_PRE, OP_COUPLING_POST, OP_EMBED_PITCH, OP_SAMPLE_PRIOR, OP_NCL_TO_NLC, OP_COPY2D, OP_PITCH_PREFIX, OP_PITCH_SOURCE,
-    OP_ATTENTION16, OP_SNAKE_CONV_GROUP_LP, OP_LSTM_STEP, OP_L2NORM_ROWS, OP_VAD_FRONTEND, OP_VAD_LSTM_SCAN, OP_COUNT
+    OP_ATTENTION16, OP_SNAKE_CONV_GROUP_LP, OP_LSTM_STEP, OP_L2NORM_ROWS, OP_VAD_FRONTEND, OP_VAD_LSTM_SCAN,
+    OP_SALIENCE_STFT, OP_SALIENCE_MAP, OP_SALIENCE_DP, OP_COUNT
 };
 const char* const OP_NAMES[OP_COUNT] = {
     "svcmi_conv_gemm_f32", "svcmi_conv_gemm_lp", "svcmi_conv_gemm_group_f32", "svcmi_conv_gemm_group_lp", "svcmi_layernorm_f32",
@@ -34,7 +35,8 @@ const char* const OP_NAMES[OP_COUNT] = {
     "svcmi_snake_conv_f32", "svcmi_snake_conv_group_f32", "svcmi_upsample_noise_f32", "svcmi_snake_post_f32", "svcmi_wn_gate_f32",
     "svcmi_coupling_pre_f32", "svcmi_coupling_post_f32", "svcmi_embed_pitch_f32", "svcmi_sample_prior_f32", "svcmi_ncl_to_nlc_f32",
     "svcmi_copy2d_f32", "svcmi_pitch_prefix_f64", "svcmi_pitch_source_f32", "svcmi_attention16", "svcmi_snake_conv_group_lp",
-    "svcmi_lstm_step_f32", "svcmi_l2norm_rows_f32", "svcmi_vad_frontend_f32", "svcmi_vad_lstm_scan_f32"};
+    "svcmi_lstm_step_f32", "svcmi_l2norm_rows_f32", "svcmi_vad_frontend_f32", "svcmi_vad_lstm_scan_f32",
+    "svcmi_salience_stft_f32", "svcmi_salience_map_f32", "svcmi_salience_dp_f64"};
 
 // ------------------------------------------------------------------------------------------------ per-launch trace (bench.py)
 struct TraceRec {
@@ -919,6 +921,32 @@ void vad_fwd(Ctx& c, const svcmi_vad_model& m, const float* audio, const int64_t
     });
 }
 
+// ------------------------------------------------------------------------------------------------ salience F0 extractor
+// pitch/core/salience.py: waveform -> path in six launches (csrc/salience.hip): the restricted STFT, the per-frame map (zero, map,
+// harmonic sum, finish) and the dynamic programme.  `z` may be the caller's [frames][n_pitch] buffer or NULL (then it lives in the workspace).
+void salience_fwd(Ctx& c, const svcmi_salience_plan& p, const float* x, int64_t n, int32_t* path, float* z) {
+    if (n < 1 || p.hop < 1 || p.n_bins < 1 || p.n_pitch < 1) { c.rc = SVCMI_EINVAL; return; }
+    const int64_t frames = 1 + n / p.hop;
+    const int widest = p.n_bins > p.n_pitch ? p.n_bins : p.n_pitch;
+    if (frames < 2) { c.rc = SVCMI_EINVAL; return; }
+    if (frames >= 0x7fffffffLL / widest) { c.rc = SVCMI_EUNSUPPORTED; return; }
+    float* X = c.ar.f(frames * p.n_bins * 2);
+    float* lf = c.ar.f(frames * p.n_pitch);
+    float* zz = z ? z : c.ar.f(frames * p.n_pitch);
+    int16_t* ptr = static_cast<int16_t*>(c.ar.take(frames * p.n_pitch * 2));
+    uint32_t* gmax = static_cast<uint32_t*>(c.ar.take(256));
+    const double cells = (double)frames * p.n_pitch;
+    run(c, OP_SALIENCE_STFT, 4.0 * frames * p.n_bins * p.n_fft, 4.0 * (n + 2.0 * p.n_fft * p.n_bins + 2.0 * frames * p.n_bins), [&] {
+        return svcmi_salience_stft_f32(&p, x, n, X, frames, c.stream);
+    });
+    run(c, OP_SALIENCE_MAP, 2.0 * cells * (p.n_bins + p.smooth_len + p.n_harm), 4.0 * (2.0 * frames * p.n_bins + 5.0 * cells), [&] {
+        return svcmi_salience_map_f32(&p, X, frames, lf, zz, gmax, c.stream);
+    });
+    run(c, OP_SALIENCE_DP, cells * p.n_pitch, 6.0 * cells, [&] {
+        return svcmi_salience_dp_f64(zz, frames, p.n_pitch, p.tol, p.log_hi, p.log_lo, ptr, path, c.stream);
+    });
+}
+
 Ctx make_ctx(void* ws, int64_t bytes, void* stream, bool plan) {
     Ctx c;
     c.stream = stream;
@@ -978,6 +1006,25 @@ extern "C" int svcmi_vad_probs_fwd(const svcmi_vad_model* m, const float* audio,
     if (((uintptr_t)workspace & 255) || workspace_bytes < svcmi_vad_workspace_bytes(batch, wmax)) return SVCMI_EINVAL;
     Ctx c = make_ctx(workspace, workspace_bytes, stream, false);
     vad_fwd(c, *m, audio, offsets, lengths, batch, wmax, state, probs);
+    return finish(c);
+}
+
+extern "C" int64_t svcmi_salience_workspace_bytes(const svcmi_salience_plan* p, int64_t n) {
+    if (!p) return SVCMI_EINVAL;
+    Ctx c = make_ctx(nullptr, 0, nullptr, true);
+    salience_fwd(c, *p, nullptr, n, nullptr, nullptr);
+    return c.rc ? (int64_t)c.rc : c.ar.peak + 256;
+}
+
+extern "C" int svcmi_salience_f0_fwd(const svcmi_salience_plan* p, const float* x, int64_t n, int32_t* path, float* z, void* workspace,
+                                     int64_t workspace_bytes, void* stream) {
+    if (!p || !x || !path || !workspace) return SVCMI_EINVAL;
+    const int64_t need = svcmi_salience_workspace_bytes(p, n);
+    if (need < 0) return (int)need;
+    if (((uintptr_t)workspace & 255) || workspace_bytes < need) return SVCMI_EINVAL;
+    if (((uintptr_t)x & 3) || ((uintptr_t)path & 3) || ((uintptr_t)z & 3)) return SVCMI_EALIGN;
+    Ctx c = make_ctx(workspace, workspace_bytes, stream, false);
+    salience_fwd(c, *p, x, n, path, z);
     return finish(c);
 }
 

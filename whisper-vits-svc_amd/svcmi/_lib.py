@@ -190,6 +190,18 @@ class VadModel(Structure):
                 ("gate1_b", c_void_p), ("dec_w", c_void_p), ("dec_b", c_float), ("reserved", c_int32)]
 
 
+class SaliencePlan(Structure):
+    """svcmi_salience_plan"""
+    _fields_ = [("basis", c_void_p), ("smooth", c_void_p), ("harm_off", c_void_p), ("harm_w", c_void_p),
+                ("n_fft", c_int32), ("hop", c_int32), ("k_lo", c_int32), ("n_bins", c_int32),
+                ("n_pitch", c_int32), ("smooth_len", c_int32), ("n_harm", c_int32), ("tol", c_int32),
+                ("fs", c_float), ("f_min", c_float), ("f_max", c_float), ("bins_per_octave", c_float),
+                ("thresh", c_double), ("log_hi", c_double), ("log_lo", c_double)]
+
+
+SALIENCE_MAX_BINS = 1024           # SVCMI_SALIENCE_MAX_BINS
+
+
 class TraceRecord(Structure):
     _fields_ = [("op", c_int32), ("ms", c_float), ("flops", c_double), ("bytes", c_double)]
 
@@ -249,6 +261,12 @@ SIGNATURES = {
     "svcmi_mask_spans_f32": (c_int, [_P, _L, _P, _I, _L, _I, _P, _L, _P]),
     "svcmi_vad_workspace_bytes": (c_int64, [_I, _I]),
     "svcmi_vad_probs_fwd": (c_int, [POINTER(VadModel), _P, _P, _P, _I, _I, _P, _P, _P, _L, _P]),
+    "svcmi_salience_plan_bytes": (c_int64, []),
+    "svcmi_salience_stft_f32": (c_int, [POINTER(SaliencePlan), _P, _L, _P, _L, _P]),
+    "svcmi_salience_map_f32": (c_int, [POINTER(SaliencePlan), _P, _L, _P, _P, _P, _P]),
+    "svcmi_salience_dp_f64": (c_int, [_P, _L, _I, _I, c_double, c_double, _P, _P, _P]),
+    "svcmi_salience_workspace_bytes": (c_int64, [POINTER(SaliencePlan), _L]),
+    "svcmi_salience_f0_fwd": (c_int, [POINTER(SaliencePlan), _P, _L, _P, _P, _P, _L, _P]),
     "svcmi_crepe_frames_f32": (c_int, [_P, _L, _I, _I, _I, _P, _I, _P]),
     "svcmi_bn_maxpool2_f32": (c_int, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _I, _I, _P]),
     "svcmi_viterbi_decode": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
@@ -312,4 +330,6 @@ def load_library(path=None):
         raise SvcmiError(f"struct layout mismatch: library {list(sizes[:n])} vs binding {mine}")
     if lib.svcmi_vad_model_bytes() != _c.sizeof(VadModel):
         raise SvcmiError(f"struct layout mismatch: svcmi_vad_model is {lib.svcmi_vad_model_bytes()} bytes in the library, {_c.sizeof(VadModel)} in the binding")
+    if lib.svcmi_salience_plan_bytes() != _c.sizeof(SaliencePlan):
+        raise SvcmiError(f"struct layout mismatch: svcmi_salience_plan is {lib.svcmi_salience_plan_bytes()} bytes in the library, {_c.sizeof(SaliencePlan)} in the binding")
     return lib

@@ -888,6 +888,67 @@ class Ops:
                    work={"bytes": 8.0 * n})
         return out
 
+    # ------------------------------------------------------------------ salience F0 extractor (csrc/salience.hip)
+    @staticmethod
+    def _salience_frames(plan, n):
+        frames = 1 + int(n) // int(plan.hop)
+        if frames < 2:
+            raise SvcmiError(f"salience: {n} samples at hop {plan.hop} give {frames} frame; the phase increment needs at least 2")
+        return frames
+
+    def salience_stft(self, plan, x):
+        """x float32 [n] (unit stride) -> complex64 [frames, n_bins]: the centred, zero-padded STFT restricted to the plan's bins
+        (svcmi_salience_stft_f32).  ``plan``: the ``struct`` of ``svcmi.pitch.core.salience.salience_plan``."""
+        self._chk(x)
+        if not (x.dim() == 1 and x.dtype == torch.float32 and (x.shape[0] <= 1 or x.stride(0) == 1)):
+            raise SvcmiError("salience_stft: x must be float32 [n] with unit stride")
+        frames = self._salience_frames(plan, x.shape[0])
+        X = torch.empty(frames, plan.n_bins, dtype=torch.complex64, device=x.device)
+        self._call("svcmi_salience_stft_f32", ctypes.byref(plan), _ptr(x), x.shape[0], _ptr(X), frames, self._stream(),
+                   work={"flops": 4.0 * frames * plan.n_bins * plan.n_fft})
+        return X
+
+    def salience_map(self, plan, X):
+        """X complex64 [frames, n_bins] -> (lf [frames, n_pitch], z [frames, n_pitch], gmax uint32-as-int32 [2]): the smoothed and
+        thresholded log-frequency spectrogram, the salience map, and the bit patterns of their maxima before thresholding."""
+        self._chk(X)
+        if not (X.dim() == 2 and X.dtype == torch.complex64 and X.is_contiguous() and X.shape[1] == plan.n_bins):
+            raise SvcmiError("salience_map: X must be a contiguous complex64 [frames, n_bins] tensor")
+        frames = X.shape[0]
+        lf = torch.empty(frames, plan.n_pitch, dtype=torch.float32, device=X.device)
+        z = torch.empty(frames, plan.n_pitch, dtype=torch.float32, device=X.device)
+        gmax = torch.empty(2, dtype=torch.int32, device=X.device)
+        self._call("svcmi_salience_map_f32", ctypes.byref(plan), _ptr(X), frames, _ptr(lf), _ptr(z), _ptr(gmax), self._stream())
+        return lf, z, gmax
+
+    def salience_dp(self, z, tol, log_hi, log_lo):
+        """z float32 [frames, n_pitch] -> path int32 [frames]: the trajectory of pitch/core/salience.py:306-349 in fp64, every
+        predecessor evaluated, lowest index on ties (svcmi_salience_dp_f64)."""
+        self._chk(z)
+        if not (z.dim() == 2 and z.dtype == torch.float32 and z.is_contiguous()):
+            raise SvcmiError("salience_dp: z must be a contiguous float32 [frames, n_pitch] tensor")
+        frames, B = z.shape
+        ptr = torch.empty(frames, B, dtype=torch.int16, device=z.device)
+        path = torch.empty(frames, dtype=torch.int32, device=z.device)
+        self._call("svcmi_salience_dp_f64", _ptr(z), frames, B, int(tol), float(log_hi), float(log_lo), _ptr(ptr), _ptr(path), self._stream())
+        return path
+
+    def salience_f0_fwd(self, plan, x, want_map=False):
+        """waveform float32 [n] -> path int32 [frames] as ONE stage call (svcmi_salience_f0_fwd); ``want_map``: also the salience map
+        [frames, n_pitch]."""
+        self._chk(x)
+        if not (x.dim() == 1 and x.dtype == torch.float32 and (x.shape[0] <= 1 or x.stride(0) == 1)):
+            raise SvcmiError("salience_f0_fwd: x must be float32 [n] with unit stride")
+        frames = self._salience_frames(plan, x.shape[0])
+        need = self.lib.svcmi_salience_workspace_bytes(ctypes.byref(plan), x.shape[0])
+        if need < 0:
+            raise SvcmiError(f"svcmi_salience_workspace_bytes failed with code {need}")
+        ws, ws_bytes = self.stage_workspace(need, x.device)
+        path = torch.empty(frames, dtype=torch.int32, device=x.device)
+        z = torch.empty(frames, plan.n_pitch, dtype=torch.float32, device=x.device) if want_map else None
+        self._stage_call("svcmi_salience_f0_fwd", ctypes.byref(plan), _ptr(x), x.shape[0], _ptr(path), _ptr(z), ws, ws_bytes, self._stream())
+        return (path, z) if want_map else path
+
     # ------------------------------------------------------------------ CREPE glue
     def crepe_frames(self, audio, hop, frame0, frames, ld=1536):
         """audio [n] -> normalised, first-layer-padded frames [frames, ld] (crepe/core.py:664-703)."""

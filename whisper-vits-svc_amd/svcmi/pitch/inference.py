@@ -198,6 +198,40 @@ def compute_f0_sing_begin(filename, device, model=None, noise=None, decoder="vit
     return finish
 
 
+def move_average(a, n, mode="same"):
+    """pitch/inference.py:10-11."""
+    return np.convolve(a, np.ones((n,)) / n, mode=mode)
+
+
+def compute_f0_salience(filename, device, ops=None):
+    """pitch/inference.py:31-44: the network-free extractor (svcmi.pitch.core.salience at Fs 16000, H 320, N 2048, 45 .. 1760 Hz), the x2
+    repeat and the 3-point moving average.  ``filename``: wav path or a 16 kHz float waveform [n] (numpy, or a tensor on any device).
+    Returns np.float64 Hz [2 * (1 + n // 320)], always voiced."""
+    return compute_f0_salience_begin(filename, device, ops=ops)()
+
+
+@torch.no_grad()
+def compute_f0_salience_begin(filename, device, ops=None):
+    """The device half of ``compute_f0_salience``, the contract of ``compute_f0_sing_begin``: STFT, salience map and trajectory are
+    ENQUEUED on the current stream and nothing waits; returns ``finish() -> np.float64 Hz`` which does the ONE device -> host copy (the
+    path) and the host tail in float64."""
+    from .core import salience as S
+    if isinstance(filename, str):
+        from ..whisper.audio import load_audio
+        audio = torch.from_numpy(load_audio(filename))
+    else:
+        audio = torch.as_tensor(filename, dtype=torch.float32)
+    ops = ops if ops is not None else S._default_ops()
+    plan = S.salience_plan(Fs=SAMPLE_RATE, N=2048, H=320, F_min=45.0, F_max=1760.0, device=device)
+    done = S.salience_begin(audio.to(device, torch.float32), plan, ops)
+
+    def finish():
+        index, _ = done()
+        f0 = np.repeat(plan.F_coef_hertz[index], 2, -1)                   # 320 -> 160 * 2 (:42)
+        return move_average(f0, 3)
+    return finish
+
+
 _VITERBI_CONSTANTS = {}
 
 

@@ -140,21 +140,32 @@ def svc_infer(model, retrieval, spk, pit, ppg, vec, hp, device, noise=None, writ
     return out if return_tensor else out.cpu().numpy()
 
 
+F0_METHODS = ("crepe", "salience")
+
+
 @torch.no_grad()
-def extract_features(audio, whisper, hubert, crepe, device, in_flight=True):
+def extract_features(audio, whisper, hubert, crepe, device, in_flight=True, f0="crepe", ops=None):
     """The three extractors of svc_inference.py:138-154 on ONE 16 kHz waveform (numpy float32 [n], or the device tensor of
     ``whisper.audio.load_audio_device``: then no extractor copies it from the host), in process and in flight together:
     the reference runs them as three child processes one after the other; they are independent, so here the Whisper PPG, the HuBERT
     units and the CREPE F0 track are issued on three HIP streams (clips-in-flight idea of svcmi/lanes.py: one network's launch gaps
     are filled by another's kernels).  Returns (ppg [T50, ppg_dim] device, vec [T50, vec_dim] device, f0 np.float32 [2 * (1 + n // 320)])
-    -- the contents of svc_tmp.ppg.npy / svc_tmp.vec.npy / svc_tmp.pit.csv (before the CSV's int() quantisation)."""
+    -- the contents of svc_tmp.ppg.npy / svc_tmp.vec.npy / svc_tmp.pit.csv (before the CSV's int() quantisation).
+    ``f0``: "crepe" (compute_f0_sing on ``crepe``) or "salience" (compute_f0_salience: no network, ``crepe`` may be None and is never
+    touched; float64 [2 * (1 + n // 320)]); ``ops``: the library the salience kernels run on (default: the process's)."""
     from .hubert import inference as hubert_inf
     from .pitch import inference as pitch_inf
     from .whisper import inference as whisper_inf
+    if f0 not in F0_METHODS:
+        raise ValueError(f"extract_features: f0 must be one of {F0_METHODS}, got {f0!r}")
     dev = torch.device(device)
+
+    def f0_begin():
+        if f0 == "salience":
+            return pitch_inf.compute_f0_salience_begin(audio, dev, ops=ops)
+        return pitch_inf.compute_f0_sing_begin(audio, dev, model=crepe)
     if dev.type != "cuda" or not in_flight:
-        return (whisper_inf.ppg_from_audio(whisper, audio), hubert_inf.units_windowed(hubert, audio),
-                pitch_inf.compute_f0_sing(audio, dev, model=crepe))
+        return (whisper_inf.ppg_from_audio(whisper, audio), hubert_inf.units_windowed(hubert, audio), f0_begin()())
     cur = torch.cuda.current_stream(dev)
     pool = whisper.__dict__.setdefault("_svcmi_extract_streams", {})          # per calling thread (folder driver workers)
     side = pool.setdefault(threading.get_ident(), [])
@@ -164,7 +175,7 @@ def extract_features(audio, whisper, hubert, crepe, device, in_flight=True):
         s.wait_stream(cur)
         if torch.is_tensor(audio) and audio.is_cuda:
             audio.record_stream(s)                # made on the current stream, read by the side streams' kernels
-    f0_finish = pitch_inf.compute_f0_sing_begin(audio, dev, model=crepe)       # the longest of the three first, on the current stream
+    f0_finish = f0_begin()                                                    # CREPE is the longest of the three: first, on the current stream
     with torch.cuda.stream(side[0]):
         ppg = whisper_inf.ppg_from_audio(whisper, audio)
     with torch.cuda.stream(side[1]):
@@ -206,19 +217,20 @@ def shift_pitch(pit, shift):
     return pit * 2 ** (shift / 12)
 
 
-def main(args):
+def main(args, device="cuda", ops=None):
     """The reference's ``main`` with the three feature extractors run IN PROCESS on the GPU instead of as
     ``os.system("python whisper|hubert|pitch/inference.py ...")`` children that each reload their model (:138-154).
     The intermediate files keep their names and formats (svc_tmp.ppg.npy / .vec.npy / .pit.csv), so ``--ppg/--vec/--pit``
     work as before; ``svc_out.wav`` (float32, hp.data.sampling_rate) and ``svc_out_pit.wav`` are written like the
-    reference does."""
+    reference does.  ``--f0 salience`` takes the F0 track from the network-free extractor (compute_f0_salience): the CREPE checkpoint is
+    never opened.  ``device`` / ``ops``: where the models live and the library they run on (tests run the whole command on the emulator)."""
     from scipy.io.wavfile import write
     from .hubert import inference as hubert_inf
     from .pitch import inference as pitch_inf
     from .vits.models import SynthesizerInfer
     from .whisper import inference as whisper_inf
-    device = "cuda"
     audio = None
+    f0_method = getattr(args, "f0", "crepe")
     f0_prec = None if getattr(args, "f0_precision", "f32") == "f32" else getattr(args, "f0_precision", "f32")
     prec = None if getattr(args, "precision", "f32") == "f32" else args.precision
 
@@ -231,28 +243,33 @@ def main(args):
         # all three features from the wav: the extractors run in flight together (extract_features); the intermediate files keep
         # their names and formats
         from .whisper.audio import load_audio, load_audio_device
-        crepe = pitch_inf.load_crepe(args.crepe, device)
-        crepe.precision = f0_prec
+        crepe = None
+        if f0_method == "crepe":
+            crepe = pitch_inf.load_crepe(args.crepe, device, ops=ops)
+            crepe.precision = f0_prec
         audio = load_audio_device(args.wave, device=device) if getattr(args, "loader", "host") == "gpu" else load_audio(args.wave)
-        ppg_d, vec_d, f0 = extract_features(audio, _with_prec(whisper_inf.load_model(args.whisper, device)),
-                                            _with_prec(hubert_inf.load_model(args.hubert, device)), crepe, device)
+        ppg_d, vec_d, f0 = extract_features(audio, _with_prec(whisper_inf.load_model(args.whisper, device, ops=ops)),
+                                            _with_prec(hubert_inf.load_model(args.hubert, device, ops=ops)), crepe, device, f0=f0_method, ops=ops)
         args.ppg, args.vec, args.pit = "svc_tmp.ppg.npy", "svc_tmp.vec.npy", "svc_tmp.pit.csv"
         np.save(args.ppg, ppg_d.cpu().numpy(), allow_pickle=False)
         np.save(args.vec, vec_d.cpu().numpy(), allow_pickle=False)
         pitch_inf.save_csv_pitch(f0, args.pit)
     if args.ppg is None:
         args.ppg = "svc_tmp.ppg.npy"
-        whisper_inf.pred_ppg(_with_prec(whisper_inf.load_model(args.whisper, device)), args.wave, args.ppg, device)
+        whisper_inf.pred_ppg(_with_prec(whisper_inf.load_model(args.whisper, device, ops=ops)), args.wave, args.ppg, device)
     if args.vec is None:
         args.vec = "svc_tmp.vec.npy"
-        hubert_inf.pred_vec(_with_prec(hubert_inf.load_model(args.hubert, device)), args.wave, args.vec, device)
+        hubert_inf.pred_vec(_with_prec(hubert_inf.load_model(args.hubert, device, ops=ops)), args.wave, args.vec, device)
     if args.pit is None:
         args.pit = "svc_tmp.pit.csv"
-        crepe = pitch_inf.load_crepe(args.crepe, device)
-        crepe.precision = f0_prec
-        pitch_inf.save_csv_pitch(pitch_inf.compute_f0_sing(args.wave, device, model=crepe), args.pit)
+        if f0_method == "salience":
+            pitch_inf.save_csv_pitch(pitch_inf.compute_f0_salience(args.wave, device, ops=ops), args.pit)
+        else:
+            crepe = pitch_inf.load_crepe(args.crepe, device, ops=ops)
+            crepe.precision = f0_prec
+            pitch_inf.save_csv_pitch(pitch_inf.compute_f0_sing(args.wave, device, model=crepe), args.pit)
     hp = load_config(args.config)
-    model = SynthesizerInfer(hp.data.filter_length // 2 + 1, hp.data.segment_size // hp.data.hop_length, hp)
+    model = SynthesizerInfer(hp.data.filter_length // 2 + 1, hp.data.segment_size // hp.data.hop_length, hp, ops=ops)
     load_svc_model(args.model, model)
     from .feature_retrieval import create_retrival
     retrieval = create_retrival(args, device)      # DummyRetrieval unless --enable-retrieval (:25-58)
@@ -304,6 +321,10 @@ def build_parser():
     p.add_argument("--hubert", type=str, default=os.path.join("hubert_pretrain", "hubert-soft-0d54a1f4.pt"))
     p.add_argument("--crepe", type=str, default=os.path.join("crepe", "assets", "full.pth"))
     p.add_argument("--debug", action="store_true")
+    p.add_argument("--f0", default="crepe", choices=list(F0_METHODS),
+                   help="F0 extractor when --pit is not given: crepe = the CREPE network (compute_f0_sing, needs --crepe); salience = the "
+                        "network-free salience extractor (compute_f0_salience: STFT, harmonic summation, one trajectory per clip); the "
+                        "CREPE checkpoint is then never opened")
     p.add_argument("--vad-post", type=str, default=None, metavar="PATH",
                    help="path of the Silero VAD archive (vad/assets/silero_vad.jit): zero the converted waveform wherever the input has no "
                         "voice, as svc_inference_post.py does, before svc_out.wav is written (off by default)")
