@@ -742,6 +742,61 @@ int64_t svcmi_salience_workspace_bytes(const svcmi_salience_plan* p, int64_t n);
 int svcmi_salience_f0_fwd(const svcmi_salience_plan* p, const float* x, int64_t n, int32_t* path, float* z, void* workspace,
                           int64_t workspace_bytes, void* stream);
 
+/* ---- pYIN F0 extractor (pitch/core/pyin.py, libf0's pYIN: the network-free extractor that decides voicing).  Added under ABI 22: purely
+ * additive.  fp64 throughout (the clip is fp32 and widens exactly).  Per frame YIN's cumulative mean normalised difference function
+ * (CMNDF) over the lags 1 .. p_max, n_thr thresholds weighted by a beta distribution into one observation column over n_pitch voiced
+ * and n_pitch unvoiced states, then ONE Viterbi pass over the clip and the refinement of every voiced frame by the closest per-threshold
+ * YIN estimate.  The device reproduces the reference as it executes under numpy, defects included.
+ * The plan is made by the host (svcmi/pitch/core/pyin.py pyin_plan); every pointer is a DEVICE pointer. */
+typedef struct svcmi_pyin_plan {
+    const double* thresholds;                       /* [n_thr], ascending */
+    const double* beta;                             /* [n_thr]: the beta-binomial weight of every threshold */
+    const double* f_axis;                           /* [n_pitch]: f_min 2^(b R / 1200) */
+    const double* band;                             /* [n_pitch][2 max_step + 1]: band[i][d] = log(A[i - max_step + d][i] + tiny), the voiced block of
+                                                       the transition matrix gathered by COLUMN (the unvoiced block is the same); entries whose
+                                                       row lies outside 0 .. n_pitch - 1 are never read */
+    int32_t n_fft, hop, p_min, p_max;               /* frame length (even), hop, max(ceil(fs / f_max), 1), ceil(fs / f_min) <= n_fft */
+    int32_t n_pitch, n_thr, max_step, reserved;
+    double fs, tol_cents;                           /* sampling rate; the refinement's tolerance R in cents */
+    double absolute_min_prob, voicing_prob;
+    double log_tiny, log_cross, log_c, tiny;        /* log(tiny), log(0.01 + tiny) (voiced <-> unvoiced), log(1 / (2 n_pitch) + tiny), tiny = 2^-1022 */
+} svcmi_pyin_plan;
+int64_t svcmi_pyin_plan_bytes(void);                /* sizeof(svcmi_pyin_plan), for a binding's layout check */
+#define SVCMI_PYIN_MAX_BINS 1024                    /* n_pitch */
+#define SVCMI_PYIN_MAX_THRESHOLDS 128               /* n_thr */
+#define SVCMI_PYIN_MAX_NFFT 4096                    /* p_max <= n_fft <= this */
+#define SVCMI_PYIN_MAX_BAND 33                      /* 2 max_step + 1 */
+
+/* The kernels (csrc/pyin.hip).  frames = 1 + n / hop for a clip of n samples.
+ *   pyin_cmndf:   x [n] fp32 -> cmndf [frames][p_max + 1] and rms [frames].  Frame m covers the samples m hop - n_fft / 2 .. + n_fft - 1 of
+ *                 x (zeros outside).  d(tau) = sum_j (x[j] - x[j + tau])^2 in its direct form, one fixed accumulation order per (frame,
+ *                 tau): the bits depend on the frame's samples alone.  cmndf[0] = 1; silence gives exact zeros, no NaN.  frames >= 2.
+ *   pyin_observe: cmndf rows -> O [frames][2 n_pitch] (time-major: the voiced half times voicing_prob, then the unvoiced constant of the
+ *                 frame), logO = log(O + tiny) (may be NULL), lag_thr and val_thr [frames][n_thr].  frames >= 1.
+ *   pyin_viterbi: logO [frames][2 n_pitch] -> path int32 [frames], numpy's argmax index for index: D[i, 0] = log_c + logO[0][i],
+ *                 D[i, t] = max_j(logA[j][i] + D[j, t - 1]) + logO[t][i], logA = band / log_cross where the matrix is not zero and
+ *                 log_tiny everywhere else; the lowest index wins among equal ROUNDED sums.  One block per clip.  ptr: int16
+ *                 [frames][2 n_pitch] scratch.  logO must not hold NaN.  frames >= 2.
+ *   pyin_finish:  path, O, rms, lag_thr, val_thr -> f0 and conf [frames].  frames >= 1.
+ * SVCMI_EINVAL before anything is launched for a null pointer (plan members included; logO of pyin_observe excepted), too few frames or
+ * frames != 1 + n / hop, n < 1, hop < 1, an odd n_fft (or < 2), p_min < 1, p_max < p_min, n_pitch / n_thr / max_step < 1,
+ * n_pitch < 2 max_step + 1, fs / tol_cents / tiny <= 0, voicing_prob outside 0 .. 1; SVCMI_EUNSUPPORTED for n_pitch, n_thr, n_fft or
+ * 2 max_step + 1 above the limits, p_max > n_fft, frames >= 2^31 / (row length); SVCMI_EALIGN for a pointer that is not aligned to its
+ * element. */
+int svcmi_pyin_cmndf_f64(const svcmi_pyin_plan* p, const float* x, int64_t n, double* cmndf, double* rms, int64_t frames, void* stream);
+int svcmi_pyin_observe_f64(const svcmi_pyin_plan* p, const double* cmndf, int64_t frames, double* O, double* logO, double* lag_thr,
+                           double* val_thr, void* stream);
+int svcmi_pyin_viterbi_f64(const double* logO, int64_t frames, int32_t n_pitch, int32_t max_step, const double* band, double log_tiny,
+                           double log_cross, double log_c, int16_t* ptr, int32_t* path, void* stream);
+int svcmi_pyin_finish_f64(const svcmi_pyin_plan* p, const int32_t* path, const double* O, const double* rms, const double* lag_thr,
+                          const double* val_thr, int64_t frames, double* f0, double* conf, void* stream);
+/* clip -> f0, conf [frames] float64 and path int32 [frames] as ONE stage call on one workspace (the CMNDF rows, logO, the back pointers,
+ * and whichever of rms [frames], O [frames][2 n_pitch], lag_thr, val_thr [frames][n_thr] the caller passes NULL for).  SVCMI_EINVAL also
+ * for a workspace that is too small or not 256-byte aligned; the query returns a negative code for a geometry the stage would refuse. */
+int64_t svcmi_pyin_workspace_bytes(const svcmi_pyin_plan* p, int64_t n);
+int svcmi_pyin_f0_fwd(const svcmi_pyin_plan* p, const float* x, int64_t n, double* f0, double* conf, int32_t* path, double* rms, double* O,
+                      double* lag_thr, double* val_thr, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- SynthesizerInfer (vits/models.py:211-256) */
 /* layer classes of the per-layer mixed-precision policy: prior encoder (enc_p: pre / hub / attention + FFN layers / proj, and its attention
  * kernel), flow (pre / in / res_skip / post of every coupling layer), the generator's trunk (conv_pre + every ups[i]), and the AMP-block

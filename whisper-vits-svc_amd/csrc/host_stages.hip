@@ -15,6 +15,8 @@
 #include "svcmi_rt.h"
 #include "../../include/svcmi.h"
 
+extern "C" int svcmi_pyin_plan_check_(const svcmi_pyin_plan* p);      // csrc/pyin.hip: the plan's own checks, for the planning pass
+
 namespace {
 
 int g_amp_grouped = 1;     // tuning / test knob ("amp_grouped", 0 | 1): 0 forces the one-launch-per-block fallback of the generator stages
@@ -27,7 +29,8 @@ enum Op {
     OP_SNAKE_ALIAS_GROUP, OP_BLOCK_MEAN, OP_SNAKE_CONV, OP_SNAKE_CONV_GROUP, OP_UPSAMPLE_NOISE, OP_SNAKE_POST, OP_WN_GATE,
     OP_COUPLING_PRE, OP_COUPLING_POST, OP_EMBED_PITCH, OP_SAMPLE_PRIOR, OP_NCL_TO_NLC, OP_COPY2D, OP_PITCH_PREFIX, OP_PITCH_SOURCE,
     OP_ATTENTION16, OP_SNAKE_CONV_GROUP_LP, OP_LSTM_STEP, OP_L2NORM_ROWS, OP_VAD_FRONTEND, OP_VAD_LSTM_SCAN,
-    OP_SALIENCE_STFT, OP_SALIENCE_MAP, OP_SALIENCE_DP, OP_COUNT
+    OP_SALIENCE_STFT, OP_SALIENCE_MAP, OP_SALIENCE_DP, OP_PYIN_CMNDF, OP_PYIN_OBSERVE, OP_PYIN_VITERBI, OP_PYIN_FINISH,
+    OP_COUNT
 };
 const char* const OP_NAMES[OP_COUNT] = {
     "svcmi_conv_gemm_f32", "svcmi_conv_gemm_lp", "svcmi_conv_gemm_group_f32", "svcmi_conv_gemm_group_lp", "svcmi_layernorm_f32",
@@ -36,7 +39,8 @@ const char* const OP_NAMES[OP_COUNT] = {
     "svcmi_coupling_pre_f32", "svcmi_coupling_post_f32", "svcmi_embed_pitch_f32", "svcmi_sample_prior_f32", "svcmi_ncl_to_nlc_f32",
     "svcmi_copy2d_f32", "svcmi_pitch_prefix_f64", "svcmi_pitch_source_f32", "svcmi_attention16", "svcmi_snake_conv_group_lp",
     "svcmi_lstm_step_f32", "svcmi_l2norm_rows_f32", "svcmi_vad_frontend_f32", "svcmi_vad_lstm_scan_f32",
-    "svcmi_salience_stft_f32", "svcmi_salience_map_f32", "svcmi_salience_dp_f64"};
+    "svcmi_salience_stft_f32", "svcmi_salience_map_f32", "svcmi_salience_dp_f64",
+    "svcmi_pyin_cmndf_f64", "svcmi_pyin_observe_f64", "svcmi_pyin_viterbi_f64", "svcmi_pyin_finish_f64"};
 
 // ------------------------------------------------------------------------------------------------ per-launch trace (bench.py)
 struct TraceRec {
@@ -947,6 +951,35 @@ void salience_fwd(Ctx& c, const svcmi_salience_plan& p, const float* x, int64_t 
     });
 }
 
+// ------------------------------------------------------------------------------------------------ pYIN F0 extractor
+// pitch/core/pyin.py: clip -> f0, conf, path in four launches (csrc/pyin.hip): CMNDF + RMS, the observation columns, Viterbi, the finish.
+// rms / O / lag_thr / val_thr may be the caller's buffers or NULL (then they live in the workspace).
+void pyin_fwd(Ctx& c, const svcmi_pyin_plan& p, const float* x, int64_t n, double* f0, double* conf, int32_t* path, double* rms, double* O,
+              double* lag_thr, double* val_thr) {
+    if (int rc = svcmi_pyin_plan_check_(&p)) { c.rc = rc; return; }
+    if (n < 1) { c.rc = SVCMI_EINVAL; return; }
+    const int64_t frames = 1 + n / p.hop, S = 2 * (int64_t)p.n_pitch, row = p.p_max + 1;
+    if (frames < 2) { c.rc = SVCMI_EINVAL; return; }
+    if (frames >= 0x7fffffffLL / (S > row ? S : row)) { c.rc = SVCMI_EUNSUPPORTED; return; }
+    auto f64 = [&](int64_t count) { return static_cast<double*>(c.ar.take(count * 8)); };
+    double* cm = f64(frames * row);
+    double* logO = f64(frames * S);
+    double* r = rms ? rms : f64(frames);
+    double* o = O ? O : f64(frames * S);
+    double* lt = lag_thr ? lag_thr : f64(frames * p.n_thr);
+    double* vt = val_thr ? val_thr : f64(frames * p.n_thr);
+    int16_t* ptr = static_cast<int16_t*>(c.ar.take(frames * S * 2));
+    const double lags = (double)frames * p.p_max, cells = (double)frames * S;
+    run(c, OP_PYIN_CMNDF, 3.0 * lags * p.n_fft, 4.0 * n + 8.0 * frames * row, [&] { return svcmi_pyin_cmndf_f64(&p, x, n, cm, r, frames, c.stream); });
+    run(c, OP_PYIN_OBSERVE, 40.0 * frames * p.n_pitch, 8.0 * (frames * row + 2.0 * cells), [&] {
+        return svcmi_pyin_observe_f64(&p, cm, frames, o, logO, lt, vt, c.stream);
+    });
+    run(c, OP_PYIN_VITERBI, cells * (2.0 * p.max_step + 4.0), 10.0 * cells, [&] {
+        return svcmi_pyin_viterbi_f64(logO, frames, p.n_pitch, p.max_step, p.band, p.log_tiny, p.log_cross, p.log_c, ptr, path, c.stream);
+    });
+    run(c, OP_PYIN_FINISH, cells, 8.0 * cells, [&] { return svcmi_pyin_finish_f64(&p, path, o, r, lt, vt, frames, f0, conf, c.stream); });
+}
+
 Ctx make_ctx(void* ws, int64_t bytes, void* stream, bool plan) {
     Ctx c;
     c.stream = stream;
@@ -1025,6 +1058,26 @@ extern "C" int svcmi_salience_f0_fwd(const svcmi_salience_plan* p, const float* 
     if (((uintptr_t)x & 3) || ((uintptr_t)path & 3) || ((uintptr_t)z & 3)) return SVCMI_EALIGN;
     Ctx c = make_ctx(workspace, workspace_bytes, stream, false);
     salience_fwd(c, *p, x, n, path, z);
+    return finish(c);
+}
+
+extern "C" int64_t svcmi_pyin_workspace_bytes(const svcmi_pyin_plan* p, int64_t n) {
+    if (!p) return SVCMI_EINVAL;
+    Ctx c = make_ctx(nullptr, 0, nullptr, true);
+    pyin_fwd(c, *p, nullptr, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    return c.rc ? (int64_t)c.rc : c.ar.peak + 256;
+}
+
+extern "C" int svcmi_pyin_f0_fwd(const svcmi_pyin_plan* p, const float* x, int64_t n, double* f0, double* conf, int32_t* path, double* rms, double* O,
+                                 double* lag_thr, double* val_thr, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!p || !x || !f0 || !conf || !path || !workspace) return SVCMI_EINVAL;
+    const int64_t need = svcmi_pyin_workspace_bytes(p, n);
+    if (need < 0) return (int)need;
+    if (((uintptr_t)workspace & 255) || workspace_bytes < need) return SVCMI_EINVAL;
+    if (((uintptr_t)x & 3) || ((uintptr_t)path & 3) || (((uintptr_t)f0 | (uintptr_t)conf | (uintptr_t)rms | (uintptr_t)O | (uintptr_t)lag_thr | (uintptr_t)val_thr) & 7))
+        return SVCMI_EALIGN;
+    Ctx c = make_ctx(workspace, workspace_bytes, stream, false);
+    pyin_fwd(c, *p, x, n, f0, conf, path, rms, O, lag_thr, val_thr);
     return finish(c);
 }
 

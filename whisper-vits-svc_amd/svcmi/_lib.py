@@ -202,6 +202,18 @@ class SaliencePlan(Structure):
 SALIENCE_MAX_BINS = 1024           # SVCMI_SALIENCE_MAX_BINS
 
 
+class PyinPlan(Structure):
+    """svcmi_pyin_plan"""
+    _fields_ = [("thresholds", c_void_p), ("beta", c_void_p), ("f_axis", c_void_p), ("band", c_void_p),
+                ("n_fft", c_int32), ("hop", c_int32), ("p_min", c_int32), ("p_max", c_int32),
+                ("n_pitch", c_int32), ("n_thr", c_int32), ("max_step", c_int32), ("reserved", c_int32),
+                ("fs", c_double), ("tol_cents", c_double), ("absolute_min_prob", c_double), ("voicing_prob", c_double),
+                ("log_tiny", c_double), ("log_cross", c_double), ("log_c", c_double), ("tiny", c_double)]
+
+
+PYIN_MAX_BINS, PYIN_MAX_THRESHOLDS, PYIN_MAX_NFFT, PYIN_MAX_BAND = 1024, 128, 4096, 33      # SVCMI_PYIN_MAX_*
+
+
 class TraceRecord(Structure):
     _fields_ = [("op", c_int32), ("ms", c_float), ("flops", c_double), ("bytes", c_double)]
 
@@ -267,6 +279,13 @@ SIGNATURES = {
     "svcmi_salience_dp_f64": (c_int, [_P, _L, _I, _I, c_double, c_double, _P, _P, _P]),
     "svcmi_salience_workspace_bytes": (c_int64, [POINTER(SaliencePlan), _L]),
     "svcmi_salience_f0_fwd": (c_int, [POINTER(SaliencePlan), _P, _L, _P, _P, _P, _L, _P]),
+    "svcmi_pyin_plan_bytes": (c_int64, []),
+    "svcmi_pyin_cmndf_f64": (c_int, [POINTER(PyinPlan), _P, _L, _P, _P, _L, _P]),
+    "svcmi_pyin_observe_f64": (c_int, [POINTER(PyinPlan), _P, _L, _P, _P, _P, _P, _P]),
+    "svcmi_pyin_viterbi_f64": (c_int, [_P, _L, _I, _I, _P, c_double, c_double, c_double, _P, _P, _P]),
+    "svcmi_pyin_finish_f64": (c_int, [POINTER(PyinPlan), _P, _P, _P, _P, _P, _L, _P, _P, _P]),
+    "svcmi_pyin_workspace_bytes": (c_int64, [POINTER(PyinPlan), _L]),
+    "svcmi_pyin_f0_fwd": (c_int, [POINTER(PyinPlan), _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "svcmi_crepe_frames_f32": (c_int, [_P, _L, _I, _I, _I, _P, _I, _P]),
     "svcmi_bn_maxpool2_f32": (c_int, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _I, _I, _P]),
     "svcmi_viterbi_decode": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
@@ -332,4 +351,6 @@ def load_library(path=None):
         raise SvcmiError(f"struct layout mismatch: svcmi_vad_model is {lib.svcmi_vad_model_bytes()} bytes in the library, {_c.sizeof(VadModel)} in the binding")
     if lib.svcmi_salience_plan_bytes() != _c.sizeof(SaliencePlan):
         raise SvcmiError(f"struct layout mismatch: svcmi_salience_plan is {lib.svcmi_salience_plan_bytes()} bytes in the library, {_c.sizeof(SaliencePlan)} in the binding")
+    if lib.svcmi_pyin_plan_bytes() != _c.sizeof(PyinPlan):
+        raise SvcmiError(f"struct layout mismatch: svcmi_pyin_plan is {lib.svcmi_pyin_plan_bytes()} bytes in the library, {_c.sizeof(PyinPlan)} in the binding")
     return lib

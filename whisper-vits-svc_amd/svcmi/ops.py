@@ -949,6 +949,73 @@ class Ops:
         self._stage_call("svcmi_salience_f0_fwd", ctypes.byref(plan), _ptr(x), x.shape[0], _ptr(path), _ptr(z), ws, ws_bytes, self._stream())
         return (path, z) if want_map else path
 
+    # ------------------------------------------------------------------ pYIN F0 extractor (csrc/pyin.hip)
+    @staticmethod
+    def _pyin_clip(name, plan, x):
+        if not (x.dim() == 1 and x.dtype == torch.float32 and (x.shape[0] <= 1 or x.stride(0) == 1)):
+            raise SvcmiError(f"{name}: x must be float32 [n] with unit stride")
+        frames = 1 + int(x.shape[0]) // int(plan.hop)
+        if frames < 2:
+            raise SvcmiError(f"{name}: {x.shape[0]} samples at hop {plan.hop} give one frame; the trajectory needs at least 2")
+        return frames
+
+    def pyin_cmndf(self, plan, x):
+        """x float32 [n] (unit stride) -> (cmndf float64 [frames, p_max + 1], rms float64 [frames]): YIN's cumulative mean normalised
+        difference function of every centred frame (svcmi_pyin_cmndf_f64).  ``plan``: the ``struct`` of ``svcmi.pitch.core.pyin.pyin_plan``."""
+        self._chk(x)
+        frames = self._pyin_clip("pyin_cmndf", plan, x)
+        cm = torch.empty(frames, plan.p_max + 1, dtype=torch.float64, device=x.device)
+        rms = torch.empty(frames, dtype=torch.float64, device=x.device)
+        self._call("svcmi_pyin_cmndf_f64", ctypes.byref(plan), _ptr(x), x.shape[0], _ptr(cm), _ptr(rms), frames, self._stream(),
+                   work={"flops": 3.0 * frames * plan.p_max * plan.n_fft})
+        return cm, rms
+
+    def pyin_observe(self, plan, cmndf, want_log=False):
+        """cmndf float64 [frames, p_max + 1] -> (O float64 [frames, 2 n_pitch], lag_thr, val_thr float64 [frames, n_thr]) and, with
+        ``want_log``, log(O + tiny) as a fourth tensor (svcmi_pyin_observe_f64)."""
+        self._chk(cmndf)
+        if not (cmndf.dim() == 2 and cmndf.dtype == torch.float64 and cmndf.is_contiguous() and cmndf.shape[1] == plan.p_max + 1 and cmndf.shape[0] >= 1):
+            raise SvcmiError("pyin_observe: cmndf must be a contiguous float64 [frames, p_max + 1] tensor")
+        frames = cmndf.shape[0]
+        new = lambda cols: torch.empty(frames, cols, dtype=torch.float64, device=cmndf.device)
+        O, lag, val = new(2 * plan.n_pitch), new(plan.n_thr), new(plan.n_thr)
+        logO = new(2 * plan.n_pitch) if want_log else None
+        self._call("svcmi_pyin_observe_f64", ctypes.byref(plan), _ptr(cmndf), frames, _ptr(O), _ptr(logO), _ptr(lag), _ptr(val), self._stream())
+        return (O, lag, val, logO) if want_log else (O, lag, val)
+
+    def pyin_viterbi(self, logO, band, log_tiny, log_cross, log_c):
+        """logO float64 [frames, 2 B] (time-major), band float64 [B, 2 max_step + 1] -> path int32 [frames]: numpy's argmax index for
+        index (svcmi_pyin_viterbi_f64)."""
+        self._chk(logO)
+        self._chk(band)
+        if not (logO.dim() == 2 and logO.dtype == torch.float64 and logO.is_contiguous() and logO.shape[1] % 2 == 0):
+            raise SvcmiError("pyin_viterbi: logO must be a contiguous float64 [frames, 2 B] tensor")
+        frames, B = logO.shape[0], logO.shape[1] // 2
+        if not (band.dim() == 2 and band.dtype == torch.float64 and band.is_contiguous() and band.shape[0] == B and band.shape[1] % 2 == 1):
+            raise SvcmiError("pyin_viterbi: band must be a contiguous float64 [B, 2 max_step + 1] tensor")
+        ptr = torch.empty(frames, 2 * B, dtype=torch.int16, device=logO.device)
+        path = torch.empty(frames, dtype=torch.int32, device=logO.device)
+        self._call("svcmi_pyin_viterbi_f64", _ptr(logO), frames, B, band.shape[1] // 2, _ptr(band), float(log_tiny), float(log_cross), float(log_c),
+                   _ptr(ptr), _ptr(path), self._stream())
+        return path
+
+    def pyin_f0_fwd(self, plan, x, want_parts=False):
+        """clip float32 [n] -> out float64 [2, frames] (f0, conf) and path int32 [frames] as ONE stage call (svcmi_pyin_f0_fwd);
+        ``want_parts``: also a dict of rms [frames], O [frames, 2 n_pitch], lag_thr and val_thr [frames, n_thr]."""
+        self._chk(x)
+        frames = self._pyin_clip("pyin_f0_fwd", plan, x)
+        need = self.lib.svcmi_pyin_workspace_bytes(ctypes.byref(plan), x.shape[0])
+        if need < 0:
+            raise SvcmiError(f"svcmi_pyin_workspace_bytes failed with code {need}")
+        ws, ws_bytes = self.stage_workspace(need, x.device)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=x.device)
+        out = new(2, frames)
+        path = torch.empty(frames, dtype=torch.int32, device=x.device)
+        parts = dict(rms=new(frames), O=new(frames, 2 * plan.n_pitch), lag_thr=new(frames, plan.n_thr), val_thr=new(frames, plan.n_thr)) if want_parts else {}
+        self._stage_call("svcmi_pyin_f0_fwd", ctypes.byref(plan), _ptr(x), x.shape[0], _ptr(out[0]), _ptr(out[1]), _ptr(path), _ptr(parts.get("rms")),
+                         _ptr(parts.get("O")), _ptr(parts.get("lag_thr")), _ptr(parts.get("val_thr")), ws, ws_bytes, self._stream())
+        return (out, path, parts) if want_parts else (out, path)
+
     # ------------------------------------------------------------------ CREPE glue
     def crepe_frames(self, audio, hop, frame0, frames, ld=1536):
         """audio [n] -> normalised, first-layer-padded frames [frames, ld] (crepe/core.py:664-703)."""

@@ -232,6 +232,35 @@ def compute_f0_salience_begin(filename, device, ops=None):
     return finish
 
 
+def compute_f0_pyin(filename, device, ops=None):
+    """The network-free extractor that decides voicing (svcmi.pitch.core.pyin at the parameters of ``compute_f0_salience``: Fs 16000,
+    N 2048, H 320, 45 .. 1760 Hz) and the x2 repeat.  The reference has no such recipe; there is NO moving average, which would smear the
+    zeros across voicing boundaries.  ``filename``: wav path or a 16 kHz float waveform [n] (numpy, or a tensor on any device).  Returns
+    np.float64 Hz [2 * (1 + n // 320)], 0 in unvoiced frames."""
+    return compute_f0_pyin_begin(filename, device, ops=ops)()
+
+
+@torch.no_grad()
+def compute_f0_pyin_begin(filename, device, ops=None):
+    """The device half of ``compute_f0_pyin``, the contract of ``compute_f0_sing_begin``: difference function, observation columns,
+    Viterbi and refinement are ENQUEUED on the current stream and nothing waits; returns ``finish() -> np.float64 Hz`` which does the ONE
+    device -> host copy and the repeat."""
+    from .core import pyin as P
+    if isinstance(filename, str):
+        from ..whisper.audio import load_audio
+        audio = torch.from_numpy(load_audio(filename))
+    else:
+        audio = torch.as_tensor(filename, dtype=torch.float32)
+    ops = ops if ops is not None else P._default_ops()
+    plan = P.pyin_plan(Fs=SAMPLE_RATE, N=2048, H=320, F_min=45.0, F_max=1760.0, device=device)
+    done = P.pyin_begin(audio.to(device, torch.float32), plan, ops)
+
+    def finish():
+        f0, _ = done()
+        return np.repeat(f0, 2, -1)                                       # 320 -> 160 * 2
+    return finish
+
+
 _VITERBI_CONSTANTS = {}
 
 

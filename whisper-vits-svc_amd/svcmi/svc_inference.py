@@ -140,7 +140,7 @@ def svc_infer(model, retrieval, spk, pit, ppg, vec, hp, device, noise=None, writ
     return out if return_tensor else out.cpu().numpy()
 
 
-F0_METHODS = ("crepe", "salience")
+F0_METHODS = ("crepe", "salience", "pyin")
 
 
 @torch.no_grad()
@@ -151,8 +151,9 @@ def extract_features(audio, whisper, hubert, crepe, device, in_flight=True, f0="
     units and the CREPE F0 track are issued on three HIP streams (clips-in-flight idea of svcmi/lanes.py: one network's launch gaps
     are filled by another's kernels).  Returns (ppg [T50, ppg_dim] device, vec [T50, vec_dim] device, f0 np.float32 [2 * (1 + n // 320)])
     -- the contents of svc_tmp.ppg.npy / svc_tmp.vec.npy / svc_tmp.pit.csv (before the CSV's int() quantisation).
-    ``f0``: "crepe" (compute_f0_sing on ``crepe``) or "salience" (compute_f0_salience: no network, ``crepe`` may be None and is never
-    touched; float64 [2 * (1 + n // 320)]); ``ops``: the library the salience kernels run on (default: the process's)."""
+    ``f0``: "crepe" (compute_f0_sing on ``crepe``), "salience" (compute_f0_salience) or "pyin" (compute_f0_pyin, 0 in unvoiced frames):
+    the latter two need no network, ``crepe`` may be None and is never touched, and they return float64 [2 * (1 + n // 320)];
+    ``ops``: the library their kernels run on (default: the process's)."""
     from .hubert import inference as hubert_inf
     from .pitch import inference as pitch_inf
     from .whisper import inference as whisper_inf
@@ -163,6 +164,8 @@ def extract_features(audio, whisper, hubert, crepe, device, in_flight=True, f0="
     def f0_begin():
         if f0 == "salience":
             return pitch_inf.compute_f0_salience_begin(audio, dev, ops=ops)
+        if f0 == "pyin":
+            return pitch_inf.compute_f0_pyin_begin(audio, dev, ops=ops)
         return pitch_inf.compute_f0_sing_begin(audio, dev, model=crepe)
     if dev.type != "cuda" or not in_flight:
         return (whisper_inf.ppg_from_audio(whisper, audio), hubert_inf.units_windowed(hubert, audio), f0_begin()())
@@ -222,8 +225,8 @@ def main(args, device="cuda", ops=None):
     ``os.system("python whisper|hubert|pitch/inference.py ...")`` children that each reload their model (:138-154).
     The intermediate files keep their names and formats (svc_tmp.ppg.npy / .vec.npy / .pit.csv), so ``--ppg/--vec/--pit``
     work as before; ``svc_out.wav`` (float32, hp.data.sampling_rate) and ``svc_out_pit.wav`` are written like the
-    reference does.  ``--f0 salience`` takes the F0 track from the network-free extractor (compute_f0_salience): the CREPE checkpoint is
-    never opened.  ``device`` / ``ops``: where the models live and the library they run on (tests run the whole command on the emulator)."""
+    reference does.  ``--f0 salience`` / ``--f0 pyin`` take the F0 track from a network-free extractor (compute_f0_salience /
+    compute_f0_pyin): the CREPE checkpoint is never opened.  ``device`` / ``ops``: where the models live and the library they run on (tests run the whole command on the emulator)."""
     from scipy.io.wavfile import write
     from .hubert import inference as hubert_inf
     from .pitch import inference as pitch_inf
@@ -264,6 +267,8 @@ def main(args, device="cuda", ops=None):
         args.pit = "svc_tmp.pit.csv"
         if f0_method == "salience":
             pitch_inf.save_csv_pitch(pitch_inf.compute_f0_salience(args.wave, device, ops=ops), args.pit)
+        elif f0_method == "pyin":
+            pitch_inf.save_csv_pitch(pitch_inf.compute_f0_pyin(args.wave, device, ops=ops), args.pit)
         else:
             crepe = pitch_inf.load_crepe(args.crepe, device, ops=ops)
             crepe.precision = f0_prec
@@ -323,8 +328,9 @@ def build_parser():
     p.add_argument("--debug", action="store_true")
     p.add_argument("--f0", default="crepe", choices=list(F0_METHODS),
                    help="F0 extractor when --pit is not given: crepe = the CREPE network (compute_f0_sing, needs --crepe); salience = the "
-                        "network-free salience extractor (compute_f0_salience: STFT, harmonic summation, one trajectory per clip); the "
-                        "CREPE checkpoint is then never opened")
+                        "network-free salience extractor (compute_f0_salience: STFT, harmonic summation, one trajectory per clip, always "
+                        "voiced); pyin = the network-free pYIN extractor (compute_f0_pyin: YIN difference function, threshold sweep, "
+                        "voiced / unvoiced HMM; 0 in unvoiced frames); with salience and pyin the CREPE checkpoint is never opened")
     p.add_argument("--vad-post", type=str, default=None, metavar="PATH",
                    help="path of the Silero VAD archive (vad/assets/silero_vad.jit): zero the converted waveform wherever the input has no "
                         "voice, as svc_inference_post.py does, before svc_out.wav is written (off by default)")
