@@ -797,6 +797,65 @@ int64_t svcmi_pyin_workspace_bytes(const svcmi_pyin_plan* p, int64_t n);
 int svcmi_pyin_f0_fwd(const svcmi_pyin_plan* p, const float* x, int64_t n, double* f0, double* conf, int32_t* path, double* rms, double* O,
                       double* lag_thr, double* val_thr, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- SWIPE' F0 extractor (pitch/core/swipe_slim.py, libf0's swipe_slim: the spectral one of the network-free extractors; it reports a
+ * pitch strength per frame).  Added under ABI 22: purely additive.  Per window size N (a power of two, hop N / 2) the magnitudes of a
+ * centred Hann STFT are resampled onto n_log log-frequency bins by a cubic spline -- a fixed linear map W_N the host tabulates --, every
+ * column is normalised and correlated with the kernel rows K_N of that window's candidates; the windows' strengths are interpolated
+ * linearly in time onto ceil(n / hop) output frames and summed with a weight per (window, candidate); the arg-max per frame is refined by
+ * a parabola.  fp32 on the matrix cores, the finish in float64.  The device reproduces the reference's two edge defects (DESIGN.md
+ * 4.11).  The plan is made by the host (svcmi/pitch/core/swipe_slim.py swipe_plan); every pointer is a DEVICE pointer.  Table rows are
+ * zero-padded to a multiple of 8 floats: ld(v) = (v + 7) & ~7. */
+#define SVCMI_SWIPE_MAX_WINDOWS 8
+#define SVCMI_SWIPE_MAX_NFFT 4096
+#define SVCMI_SWIPE_MAX_LOGBINS 1024                /* n_log */
+#define SVCMI_SWIPE_MAX_CANDIDATES 1024             /* n_pitch */
+typedef struct svcmi_swipe_window {
+    const float* basis;                             /* [n_fft][2 (n_fft / 2 + 1)]: hann[i] cos(2 pi i k / n_fft) at column 2k, -hann[i] sin(..) at 2k + 1 */
+    const float* resample;                          /* W_N [n_log][ld(n_fft / 2 + 1)]: the cubic spline from the linear to the log axis */
+    const float* kernels;                           /* K_N [n_cand][ld(n_log)]: the kernel rows of this window's candidates */
+    const int32_t* cand;                            /* [n_cand]: the candidate index of every row, strictly ascending, < n_pitch */
+    const float* mu;                                /* [n_cand]: 1 - |err - octave| */
+    int32_t n_fft, n_cand;
+} svcmi_swipe_window;
+typedef struct svcmi_swipe_plan {
+    svcmi_swipe_window win[SVCMI_SWIPE_MAX_WINDOWS]; /* ascending n_fft: the order in which the strengths are summed */
+    int32_t n_win, hop, n_log, n_pitch;             /* windows, output hop H, log-frequency bins, pitch candidates B */
+    double f_min, step, threshold;                  /* F_min; R / 1200 (octaves per candidate); strength_threshold */
+} svcmi_swipe_plan;
+int64_t svcmi_swipe_plan_bytes(void);               /* sizeof(svcmi_swipe_plan), for a binding's layout check */
+
+/* The kernels (csrc/swipe.hip).  For a clip of n samples window w has 1 + (n + N) / (N / 2) frames (svcmi_swipe_frames(p, w, n)) and the
+ * output has ceil(n / hop) (window = -1).
+ *   swipe_mag:      x [n] fp32 -> Y [frames_w][ld(N / 2 + 1)]: |STFT| of x padded with N zeros at the end, centred (N / 2 zeros in front,
+ *                   index arithmetic), Hann, hop N / 2, all N / 2 + 1 bins; the pad columns are written as zeros.  One ascending
+ *                   accumulation chain per output: the bits depend on the frame's samples alone.
+ *   swipe_resample: Y -> L [frames][ld(n_log)] = W_N Y per frame (pad columns zero), one fixed accumulation order per output.
+ *   swipe_strength: L -> SN [frames][n_cand] = K_N L / (sqrt(sum_f L^2) + eps) per frame, eps = 2^-52; the norm in one fixed order.
+ *   swipe_accum:    SN of all windows back to back (window w at the float offset sum_{v < w} frames_v n_cand_v) -> S [ceil(n / hop)][n_pitch]:
+ *                   S[j][cand[c]] = sum over the windows in ascending order of mu[c] (s0 + w (s1 - s0)), the two frames around j hop / (N / 2).
+ *   swipe_finish:   S [frames][n_pitch] -> f0, conf float64 [frames], amax int32 [frames] (may be NULL), flags uint32 [1].  Arg-max with
+ *                   the lowest index on ties; S[i - 1] at i = 0 is S[n_pitch - 1] (numpy's wrap); shift = -b / (2 a), a = eps + (y1 + y3 -
+ *                   2 y2) / 2, b = (y3 - y1) / 2; f0 = f_min 2^(step (i + shift)), 0 where conf = S[i] < threshold.  A frame whose arg-max
+ *                   is n_pitch - 1 takes shift 0 and adds 1 to flags[0] (zeroed first): the reference raises IndexError for such a clip.
+ *                   S must not hold NaN.
+ * SVCMI_EINVAL before anything is launched for a null pointer (plan members included), n < 1, frames < 1, a window index outside the
+ * plan, n_win outside 1 .. 8, n_fft no power of two in 8 .. 4096, n_log outside 2 .. 1024, n_pitch outside 1 .. 1024, n_cand outside
+ * 1 .. n_pitch, hop < 1, f_min or step <= 0, a NaN threshold; SVCMI_EALIGN for a pointer that is not aligned to its element (16 bytes
+ * for resample, kernels, Y and L); SVCMI_EUNSUPPORTED for n >= 2^31 - 16384. */
+int64_t svcmi_swipe_frames(const svcmi_swipe_plan* p, int32_t window, int64_t n);
+int svcmi_swipe_mag_f32(const svcmi_swipe_plan* p, int32_t window, const float* x, int64_t n, float* Y, void* stream);
+int svcmi_swipe_resample_f32(const svcmi_swipe_plan* p, int32_t window, const float* Y, int64_t frames, float* L, void* stream);
+int svcmi_swipe_strength_f32(const svcmi_swipe_plan* p, int32_t window, const float* L, int64_t frames, float* SN, void* stream);
+int svcmi_swipe_accum_f32(const svcmi_swipe_plan* p, const float* SN, int64_t n, float* S, void* stream);
+int svcmi_swipe_finish_f64(const float* S, int64_t frames, int32_t n_pitch, int32_t n_log, double f_min, double step, double threshold,
+                           double* f0, double* conf, int32_t* amax, uint32_t* flags, void* stream);
+/* clip -> f0, conf float64 [ceil(n / hop)] and the flag word as ONE stage call on one workspace (Y and L of the largest window, every
+ * window's SN, and S when the caller passes NULL for it): 3 launches per window, then accum, zero, finish.  SVCMI_EINVAL also for a
+ * workspace that is too small or not 256-byte aligned; the query returns a negative code for a geometry the stage would refuse. */
+int64_t svcmi_swipe_workspace_bytes(const svcmi_swipe_plan* p, int64_t n);
+int svcmi_swipe_f0_fwd(const svcmi_swipe_plan* p, const float* x, int64_t n, double* f0, double* conf, float* S, uint32_t* flags,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- SynthesizerInfer (vits/models.py:211-256) */
 /* layer classes of the per-layer mixed-precision policy: prior encoder (enc_p: pre / hub / attention + FFN layers / proj, and its attention
  * kernel), flow (pre / in / res_skip / post of every coupling layer), the generator's trunk (conv_pre + every ups[i]), and the AMP-block

@@ -214,6 +214,22 @@ class PyinPlan(Structure):
 PYIN_MAX_BINS, PYIN_MAX_THRESHOLDS, PYIN_MAX_NFFT, PYIN_MAX_BAND = 1024, 128, 4096, 33      # SVCMI_PYIN_MAX_*
 
 
+class SwipeWindow(Structure):
+    """svcmi_swipe_window"""
+    _fields_ = [("basis", c_void_p), ("resample", c_void_p), ("kernels", c_void_p), ("cand", c_void_p), ("mu", c_void_p),
+                ("n_fft", c_int32), ("n_cand", c_int32)]
+
+
+SWIPE_MAX_WINDOWS, SWIPE_MAX_NFFT, SWIPE_MAX_LOGBINS, SWIPE_MAX_CANDIDATES = 8, 4096, 1024, 1024      # SVCMI_SWIPE_MAX_*
+
+
+class SwipePlan(Structure):
+    """svcmi_swipe_plan"""
+    _fields_ = [("win", SwipeWindow * SWIPE_MAX_WINDOWS),
+                ("n_win", c_int32), ("hop", c_int32), ("n_log", c_int32), ("n_pitch", c_int32),
+                ("f_min", c_double), ("step", c_double), ("threshold", c_double)]
+
+
 class TraceRecord(Structure):
     _fields_ = [("op", c_int32), ("ms", c_float), ("flops", c_double), ("bytes", c_double)]
 
@@ -286,6 +302,15 @@ SIGNATURES = {
     "svcmi_pyin_finish_f64": (c_int, [POINTER(PyinPlan), _P, _P, _P, _P, _P, _L, _P, _P, _P]),
     "svcmi_pyin_workspace_bytes": (c_int64, [POINTER(PyinPlan), _L]),
     "svcmi_pyin_f0_fwd": (c_int, [POINTER(PyinPlan), _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "svcmi_swipe_plan_bytes": (c_int64, []),
+    "svcmi_swipe_frames": (c_int64, [POINTER(SwipePlan), _I, _L]),
+    "svcmi_swipe_mag_f32": (c_int, [POINTER(SwipePlan), _I, _P, _L, _P, _P]),
+    "svcmi_swipe_resample_f32": (c_int, [POINTER(SwipePlan), _I, _P, _L, _P, _P]),
+    "svcmi_swipe_strength_f32": (c_int, [POINTER(SwipePlan), _I, _P, _L, _P, _P]),
+    "svcmi_swipe_accum_f32": (c_int, [POINTER(SwipePlan), _P, _L, _P, _P]),
+    "svcmi_swipe_finish_f64": (c_int, [_P, _L, _I, _I, c_double, c_double, c_double, _P, _P, _P, _P, _P]),
+    "svcmi_swipe_workspace_bytes": (c_int64, [POINTER(SwipePlan), _L]),
+    "svcmi_swipe_f0_fwd": (c_int, [POINTER(SwipePlan), _P, _L, _P, _P, _P, _P, _P, _L, _P]),
     "svcmi_crepe_frames_f32": (c_int, [_P, _L, _I, _I, _I, _P, _I, _P]),
     "svcmi_bn_maxpool2_f32": (c_int, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _I, _I, _P]),
     "svcmi_viterbi_decode": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
@@ -353,4 +378,6 @@ def load_library(path=None):
         raise SvcmiError(f"struct layout mismatch: svcmi_salience_plan is {lib.svcmi_salience_plan_bytes()} bytes in the library, {_c.sizeof(SaliencePlan)} in the binding")
     if lib.svcmi_pyin_plan_bytes() != _c.sizeof(PyinPlan):
         raise SvcmiError(f"struct layout mismatch: svcmi_pyin_plan is {lib.svcmi_pyin_plan_bytes()} bytes in the library, {_c.sizeof(PyinPlan)} in the binding")
+    if lib.svcmi_swipe_plan_bytes() != _c.sizeof(SwipePlan):
+        raise SvcmiError(f"struct layout mismatch: svcmi_swipe_plan is {lib.svcmi_swipe_plan_bytes()} bytes in the library, {_c.sizeof(SwipePlan)} in the binding")
     return lib

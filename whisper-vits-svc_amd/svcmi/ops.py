@@ -1016,6 +1016,97 @@ class Ops:
                          _ptr(parts.get("O")), _ptr(parts.get("lag_thr")), _ptr(parts.get("val_thr")), ws, ws_bytes, self._stream())
         return (out, path, parts) if want_parts else (out, path)
 
+    # ------------------------------------------------------------------ SWIPE' F0 extractor (csrc/swipe.hip)
+    def _swipe_frames(self, plan, window, n):
+        frames = self.lib.svcmi_swipe_frames(ctypes.byref(plan), int(window), int(n))
+        if frames < 0:
+            raise SvcmiError(f"svcmi_swipe_frames failed with code {frames}")
+        return int(frames)
+
+    @staticmethod
+    def _swipe_rows(name, t, cols):
+        if not (t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous() and t.shape[1] == cols and t.shape[0] >= 1):
+            raise SvcmiError(f"{name}: expected a contiguous float32 [frames, {cols}] tensor, got {tuple(t.shape)}")
+
+    def swipe_mag(self, plan, window, x):
+        """x float32 [n] (unit stride) -> Y float32 [frames_w, ld(N / 2 + 1)]: the centred Hann STFT magnitudes of the end-padded clip at
+        window ``window`` of the plan, pad columns zero (svcmi_swipe_mag_f32).  ``plan``: the ``struct`` of ``swipe_plan``."""
+        self._chk(x)
+        if not (x.dim() == 1 and x.dtype == torch.float32 and (x.shape[0] <= 1 or x.stride(0) == 1)):
+            raise SvcmiError("swipe_mag: x must be float32 [n] with unit stride")
+        frames = self._swipe_frames(plan, window, x.shape[0])
+        N = plan.win[window].n_fft
+        Y = torch.empty(frames, (N // 2 + 8) & ~7, dtype=torch.float32, device=x.device)
+        self._call("svcmi_swipe_mag_f32", ctypes.byref(plan), int(window), _ptr(x), x.shape[0], _ptr(Y), self._stream(),
+                   work={"flops": 4.0 * frames * (N // 2 + 1) * N})
+        return Y
+
+    def swipe_resample(self, plan, window, Y):
+        """Y float32 [frames, ld(N / 2 + 1)] -> L float32 [frames, ld(n_log)] = W_N Y per frame (svcmi_swipe_resample_f32)."""
+        self._chk(Y)
+        self._swipe_rows("swipe_resample", Y, (plan.win[window].n_fft // 2 + 8) & ~7)
+        L = torch.empty(Y.shape[0], (plan.n_log + 7) & ~7, dtype=torch.float32, device=Y.device)
+        self._call("svcmi_swipe_resample_f32", ctypes.byref(plan), int(window), _ptr(Y), Y.shape[0], _ptr(L), self._stream(),
+                   work={"flops": 2.0 * Y.shape[0] * Y.shape[1] * plan.n_log})
+        return L
+
+    def swipe_strength(self, plan, window, L):
+        """L float32 [frames, ld(n_log)] -> S_N float32 [frames, n_cand] = K_N L / (||L|| + eps) per frame (svcmi_swipe_strength_f32)."""
+        self._chk(L)
+        self._swipe_rows("swipe_strength", L, (plan.n_log + 7) & ~7)
+        SN = torch.empty(L.shape[0], plan.win[window].n_cand, dtype=torch.float32, device=L.device)
+        self._call("svcmi_swipe_strength_f32", ctypes.byref(plan), int(window), _ptr(L), L.shape[0], _ptr(SN), self._stream(),
+                   work={"flops": 2.0 * L.shape[0] * L.shape[1] * SN.shape[1]})
+        return SN
+
+    def swipe_accum(self, plan, parts, n):
+        """parts: the windows' S_N in the plan's order, for a clip of ``n`` samples -> S float32 [ceil(n / hop), n_pitch]: linear
+        interpolation in time and the weighted sum, smallest window first (svcmi_swipe_accum_f32)."""
+        self._chk(*parts)
+        if len(parts) != plan.n_win:
+            raise SvcmiError(f"swipe_accum: {len(parts)} parts for {plan.n_win} windows")
+        for w, t in enumerate(parts):
+            self._swipe_rows("swipe_accum", t, plan.win[w].n_cand)
+            if t.shape[0] != self._swipe_frames(plan, w, n):
+                raise SvcmiError(f"swipe_accum: window {w} has {t.shape[0]} frames, a clip of {n} samples gives {self._swipe_frames(plan, w, n)}")
+        sn = torch.cat([t.reshape(-1) for t in parts])
+        S = torch.empty(self._swipe_frames(plan, -1, n), plan.n_pitch, dtype=torch.float32, device=sn.device)
+        self._call("svcmi_swipe_accum_f32", ctypes.byref(plan), _ptr(sn), int(n), _ptr(S), self._stream())
+        return S
+
+    def swipe_finish(self, S, n_log, f_min, step, threshold=0.0):
+        """S float32 [frames, B] -> (out float64 [2, frames] = f0, conf; amax int32 [frames]; flags int32 [1], the number of frames whose
+        arg-max is B - 1): svcmi_swipe_finish_f64."""
+        self._chk(S)
+        if not (S.dim() == 2 and S.dtype == torch.float32 and S.is_contiguous() and S.shape[0] >= 1):
+            raise SvcmiError("swipe_finish: S must be a contiguous float32 [frames, B] tensor")
+        frames, B = S.shape
+        out = torch.empty(2, frames, dtype=torch.float64, device=S.device)
+        amax = torch.empty(frames, dtype=torch.int32, device=S.device)
+        flags = torch.empty(1, dtype=torch.int32, device=S.device)
+        self._call("svcmi_swipe_finish_f64", _ptr(S), frames, B, int(n_log), float(f_min), float(step), float(threshold), _ptr(out[0]), _ptr(out[1]),
+                   _ptr(amax), _ptr(flags), self._stream())
+        return out, amax, flags
+
+    def swipe_f0_fwd(self, plan, x, want_map=False):
+        """clip float32 [n] -> out float64 [3, frames] (f0, conf, and the flag word as a float64 in every cell of the third row, so that
+        ONE device -> host copy carries everything) as one stage call (svcmi_swipe_f0_fwd); ``want_map``: also S [frames, n_pitch]."""
+        self._chk(x)
+        if not (x.dim() == 1 and x.dtype == torch.float32 and (x.shape[0] <= 1 or x.stride(0) == 1)):
+            raise SvcmiError("swipe_f0_fwd: x must be float32 [n] with unit stride")
+        need = self.lib.svcmi_swipe_workspace_bytes(ctypes.byref(plan), x.shape[0])
+        if need < 0:
+            raise SvcmiError(f"svcmi_swipe_workspace_bytes failed with code {need}")
+        frames = self._swipe_frames(plan, -1, x.shape[0])
+        ws, ws_bytes = self.stage_workspace(need, x.device)
+        out = torch.empty(3, frames, dtype=torch.float64, device=x.device)
+        flags = torch.empty(1, dtype=torch.int32, device=x.device)
+        S = torch.empty(frames, plan.n_pitch, dtype=torch.float32, device=x.device) if want_map else None
+        self._stage_call("svcmi_swipe_f0_fwd", ctypes.byref(plan), _ptr(x), x.shape[0], _ptr(out[0]), _ptr(out[1]), _ptr(S), _ptr(flags), ws, ws_bytes,
+                         self._stream())
+        out[2] = flags.to(torch.float64)
+        return (out, S) if want_map else out
+
     # ------------------------------------------------------------------ CREPE glue
     def crepe_frames(self, audio, hop, frame0, frames, ld=1536):
         """audio [n] -> normalised, first-layer-padded frames [frames, ld] (crepe/core.py:664-703)."""

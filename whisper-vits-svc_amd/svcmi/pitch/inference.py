@@ -261,6 +261,38 @@ def compute_f0_pyin_begin(filename, device, ops=None):
     return finish
 
 
+def compute_f0_swipe(filename, device, strength_threshold=0.0, ops=None):
+    """libf0's SWIPE' (svcmi.pitch.core.swipe_slim at the parameters of ``compute_f0_salience``: Fs 16000, H 320, 45 .. 1760 Hz) and the x2
+    repeat.  The reference has no such recipe.  ``edge="clamp"``: a frame whose arg-max is the last candidate takes that candidate's
+    frequency instead of the reference's IndexError for the whole clip.  There is NO moving average, for ``compute_f0_pyin``'s reason: with
+    a ``strength_threshold`` above 0 the track holds zeros, which it would smear.  ``filename``: wav path or a 16 kHz float waveform [n]
+    (numpy, or a tensor on any device).  Returns np.float64 Hz [2 * ceil(n / 320)] -- one frame (two values) shorter than the salience and
+    pYIN tracks when 320 divides n --, 0 where the pitch strength is below ``strength_threshold`` (at 0, libf0's default, every frame is
+    voiced, silence included: 45 Hz)."""
+    return compute_f0_swipe_begin(filename, device, strength_threshold=strength_threshold, ops=ops)()
+
+
+@torch.no_grad()
+def compute_f0_swipe_begin(filename, device, strength_threshold=0.0, ops=None):
+    """The device half of ``compute_f0_swipe``, the contract of ``compute_f0_sing_begin``: the STFTs, products, interpolation and the finish
+    are ENQUEUED on the current stream and nothing waits; returns ``finish() -> np.float64 Hz`` which does the ONE device -> host copy and
+    the repeat."""
+    from .core import swipe_slim as W
+    if isinstance(filename, str):
+        from ..whisper.audio import load_audio
+        audio = torch.from_numpy(load_audio(filename))
+    else:
+        audio = torch.as_tensor(filename, dtype=torch.float32)
+    ops = ops if ops is not None else W._default_ops()
+    plan = W.swipe_plan(Fs=SAMPLE_RATE, H=320, F_min=45.0, F_max=1760.0, R=10, strength_threshold=strength_threshold, device=device)
+    done = W.swipe_begin(audio.to(device, torch.float32), plan, ops, edge="clamp")
+
+    def finish():
+        f0, _ = done()
+        return np.repeat(f0, 2, -1)                                       # 320 -> 160 * 2
+    return finish
+
+
 _VITERBI_CONSTANTS = {}
 
 

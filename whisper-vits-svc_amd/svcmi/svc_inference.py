@@ -141,10 +141,11 @@ def svc_infer(model, retrieval, spk, pit, ppg, vec, hp, device, noise=None, writ
 
 
 F0_METHODS = ("crepe", "salience", "pyin")
+F0_CHOICES = F0_METHODS + ("swipe",)       # what --f0 and extract_features take (F0_METHODS keeps the value its users pin)
 
 
 @torch.no_grad()
-def extract_features(audio, whisper, hubert, crepe, device, in_flight=True, f0="crepe", ops=None):
+def extract_features(audio, whisper, hubert, crepe, device, in_flight=True, f0="crepe", ops=None, swipe_threshold=0.0):
     """The three extractors of svc_inference.py:138-154 on ONE 16 kHz waveform (numpy float32 [n], or the device tensor of
     ``whisper.audio.load_audio_device``: then no extractor copies it from the host), in process and in flight together:
     the reference runs them as three child processes one after the other; they are independent, so here the Whisper PPG, the HuBERT
@@ -153,12 +154,14 @@ def extract_features(audio, whisper, hubert, crepe, device, in_flight=True, f0="
     -- the contents of svc_tmp.ppg.npy / svc_tmp.vec.npy / svc_tmp.pit.csv (before the CSV's int() quantisation).
     ``f0``: "crepe" (compute_f0_sing on ``crepe``), "salience" (compute_f0_salience) or "pyin" (compute_f0_pyin, 0 in unvoiced frames):
     the latter two need no network, ``crepe`` may be None and is never touched, and they return float64 [2 * (1 + n // 320)];
+    "swipe" (compute_f0_swipe with ``swipe_threshold``, network-free too) returns float64 [2 * ceil(n / 320)], one frame shorter when 320
+    divides n: ``svc_infer`` trims all three features to the shortest, which is where every track's length is settled;
     ``ops``: the library their kernels run on (default: the process's)."""
     from .hubert import inference as hubert_inf
     from .pitch import inference as pitch_inf
     from .whisper import inference as whisper_inf
-    if f0 not in F0_METHODS:
-        raise ValueError(f"extract_features: f0 must be one of {F0_METHODS}, got {f0!r}")
+    if f0 not in F0_CHOICES:
+        raise ValueError(f"extract_features: f0 must be one of {F0_CHOICES}, got {f0!r}")
     dev = torch.device(device)
 
     def f0_begin():
@@ -166,6 +169,8 @@ def extract_features(audio, whisper, hubert, crepe, device, in_flight=True, f0="
             return pitch_inf.compute_f0_salience_begin(audio, dev, ops=ops)
         if f0 == "pyin":
             return pitch_inf.compute_f0_pyin_begin(audio, dev, ops=ops)
+        if f0 == "swipe":
+            return pitch_inf.compute_f0_swipe_begin(audio, dev, strength_threshold=swipe_threshold, ops=ops)
         return pitch_inf.compute_f0_sing_begin(audio, dev, model=crepe)
     if dev.type != "cuda" or not in_flight:
         return (whisper_inf.ppg_from_audio(whisper, audio), hubert_inf.units_windowed(hubert, audio), f0_begin()())
@@ -225,8 +230,8 @@ def main(args, device="cuda", ops=None):
     ``os.system("python whisper|hubert|pitch/inference.py ...")`` children that each reload their model (:138-154).
     The intermediate files keep their names and formats (svc_tmp.ppg.npy / .vec.npy / .pit.csv), so ``--ppg/--vec/--pit``
     work as before; ``svc_out.wav`` (float32, hp.data.sampling_rate) and ``svc_out_pit.wav`` are written like the
-    reference does.  ``--f0 salience`` / ``--f0 pyin`` take the F0 track from a network-free extractor (compute_f0_salience /
-    compute_f0_pyin): the CREPE checkpoint is never opened.  ``device`` / ``ops``: where the models live and the library they run on (tests run the whole command on the emulator)."""
+    reference does.  ``--f0 salience`` / ``--f0 pyin`` / ``--f0 swipe`` take the F0 track from a network-free extractor (compute_f0_salience /
+    compute_f0_pyin / compute_f0_swipe with ``--swipe-threshold``): the CREPE checkpoint is never opened.  ``device`` / ``ops``: where the models live and the library they run on (tests run the whole command on the emulator)."""
     from scipy.io.wavfile import write
     from .hubert import inference as hubert_inf
     from .pitch import inference as pitch_inf
@@ -236,6 +241,7 @@ def main(args, device="cuda", ops=None):
     f0_method = getattr(args, "f0", "crepe")
     f0_prec = None if getattr(args, "f0_precision", "f32") == "f32" else getattr(args, "f0_precision", "f32")
     prec = None if getattr(args, "precision", "f32") == "f32" else args.precision
+    swipe_thr = float(getattr(args, "swipe_threshold", 0.0))
 
     enc_prec = "f16" if prec == "mixed" else prec      # the mixed policy's classes are the synthesizer's; the extractors follow the reference's .half()
 
@@ -252,7 +258,8 @@ def main(args, device="cuda", ops=None):
             crepe.precision = f0_prec
         audio = load_audio_device(args.wave, device=device) if getattr(args, "loader", "host") == "gpu" else load_audio(args.wave)
         ppg_d, vec_d, f0 = extract_features(audio, _with_prec(whisper_inf.load_model(args.whisper, device, ops=ops)),
-                                            _with_prec(hubert_inf.load_model(args.hubert, device, ops=ops)), crepe, device, f0=f0_method, ops=ops)
+                                            _with_prec(hubert_inf.load_model(args.hubert, device, ops=ops)), crepe, device, f0=f0_method, ops=ops,
+                                            swipe_threshold=swipe_thr)
         args.ppg, args.vec, args.pit = "svc_tmp.ppg.npy", "svc_tmp.vec.npy", "svc_tmp.pit.csv"
         np.save(args.ppg, ppg_d.cpu().numpy(), allow_pickle=False)
         np.save(args.vec, vec_d.cpu().numpy(), allow_pickle=False)
@@ -269,6 +276,8 @@ def main(args, device="cuda", ops=None):
             pitch_inf.save_csv_pitch(pitch_inf.compute_f0_salience(args.wave, device, ops=ops), args.pit)
         elif f0_method == "pyin":
             pitch_inf.save_csv_pitch(pitch_inf.compute_f0_pyin(args.wave, device, ops=ops), args.pit)
+        elif f0_method == "swipe":
+            pitch_inf.save_csv_pitch(pitch_inf.compute_f0_swipe(args.wave, device, strength_threshold=swipe_thr, ops=ops), args.pit)
         else:
             crepe = pitch_inf.load_crepe(args.crepe, device, ops=ops)
             crepe.precision = f0_prec
@@ -326,11 +335,16 @@ def build_parser():
     p.add_argument("--hubert", type=str, default=os.path.join("hubert_pretrain", "hubert-soft-0d54a1f4.pt"))
     p.add_argument("--crepe", type=str, default=os.path.join("crepe", "assets", "full.pth"))
     p.add_argument("--debug", action="store_true")
-    p.add_argument("--f0", default="crepe", choices=list(F0_METHODS),
+    p.add_argument("--f0", default="crepe", choices=list(F0_CHOICES),
                    help="F0 extractor when --pit is not given: crepe = the CREPE network (compute_f0_sing, needs --crepe); salience = the "
                         "network-free salience extractor (compute_f0_salience: STFT, harmonic summation, one trajectory per clip, always "
                         "voiced); pyin = the network-free pYIN extractor (compute_f0_pyin: YIN difference function, threshold sweep, "
-                        "voiced / unvoiced HMM; 0 in unvoiced frames); with salience and pyin the CREPE checkpoint is never opened")
+                        "voiced / unvoiced HMM; 0 in unvoiced frames); swipe = libf0's SWIPE' (compute_f0_swipe: log-frequency spectrum "
+                        "against prime-harmonic sawtooth kernels at six window sizes; voiced wherever the pitch strength reaches "
+                        "--swipe-threshold); with salience, pyin and swipe the CREPE checkpoint is never opened")
+    p.add_argument("--swipe-threshold", type=float, default=0.0,
+                   help="--f0 swipe: frames whose pitch strength (a normalised correlation in -1 .. 1) is below this get F0 = 0; "
+                        "default 0, libf0's")
     p.add_argument("--vad-post", type=str, default=None, metavar="PATH",
                    help="path of the Silero VAD archive (vad/assets/silero_vad.jit): zero the converted waveform wherever the input has no "
                         "voice, as svc_inference_post.py does, before svc_out.wav is written (off by default)")

@@ -50,7 +50,7 @@ class Converter:
         self.whisper = whisper_inf.load_model({"dims": dims[0], "model_state_dict": bc(wck["model_state_dict"] if rank == 0 else None)}, device)
         self.hubert = hubert_inf.load_model(bc(_load_on_rank0(args.hubert, rank)), device)
         self.f0 = getattr(args, "f0", "crepe")
-        self.crepe = None                   # --f0 salience / pyin: the CREPE checkpoint is never opened
+        self.crepe = None                   # --f0 salience / pyin / swipe: the CREPE checkpoint is never opened
         if self.f0 == "crepe":
             self.crepe = pitch_inf.load_crepe(bc(_load_on_rank0(args.crepe, rank)), device)
             self.crepe.precision = None if getattr(args, "f0_precision", "f32") == "f32" else getattr(args, "f0_precision", "f32")
@@ -89,7 +89,8 @@ class Converter:
         # carry the same values: float32 arrays and the int()-quantised F0 of the pitch CSV, svc_inference.py:150-154,183)
         gpu_loader = getattr(self.args, "loader", "host") == "gpu" and torch.device(self.device).type == "cuda"
         audio = load_audio_device(wav_path, device=self.device) if gpu_loader else load_audio(wav_path)
-        ppg, vec, pit = extract_features(audio, self.whisper, self.hubert, self.crepe, self.device, f0=self.f0)
+        ppg, vec, pit = extract_features(audio, self.whisper, self.hubert, self.crepe, self.device, f0=self.f0,
+                                             swipe_threshold=float(getattr(self.args, "swipe_threshold", 0.0)))
         ppg = torch.repeat_interleave(ppg, 2, 0)              # np.repeat(ppg, 2, 0), svc_inference.py:175-182
         vec = torch.repeat_interleave(vec, 2, 0)
         pit = torch.FloatTensor(shift_pitch(pitch_inf.quantize_pitch_like_csv(pit), self.args.shift))
@@ -164,9 +165,10 @@ def build_parser():
     p.add_argument("--whisper", type=str, default=os.path.join("whisper_pretrain", "large-v2.pt"))
     p.add_argument("--hubert", type=str, default=os.path.join("hubert_pretrain", "hubert-soft-0d54a1f4.pt"))
     p.add_argument("--crepe", type=str, default=os.path.join("crepe", "assets", "full.pth"))
-    p.add_argument("--f0", default="crepe", choices=["crepe", "salience", "pyin"],
-                   help="F0 extractor: crepe = the CREPE network (needs --crepe); salience / pyin = the network-free salience and pYIN "
-                        "extractors (see svc_inference)")
+    p.add_argument("--f0", default="crepe", choices=["crepe", "salience", "pyin", "swipe"],
+                   help="F0 extractor: crepe = the CREPE network (needs --crepe); salience / pyin / swipe = the network-free salience, pYIN "
+                        "and SWIPE' extractors (see svc_inference)")
+    p.add_argument("--swipe-threshold", type=float, default=0.0, help="--f0 swipe: pitch-strength threshold below which F0 = 0 (see svc_inference)")
     p.add_argument("--precision", default="f32", choices=["f32", "bf16x3", "bf16", "f16", "mixed"],
                    help="GEMM operand precision of Whisper / HuBERT / synthesizer (see svc_inference); f32 = parity default")
     p.add_argument("--f0-precision", default="f32", choices=["f32", "bf16x3", "f16", "bf16"], help="GEMM operand precision of the CREPE F0 extractor (see svc_inference)")
