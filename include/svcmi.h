@@ -797,6 +797,51 @@ int64_t svcmi_pyin_workspace_bytes(const svcmi_pyin_plan* p, int64_t n);
 int svcmi_pyin_f0_fwd(const svcmi_pyin_plan* p, const float* x, int64_t n, double* f0, double* conf, int32_t* path, double* rms, double* O,
                       double* lag_thr, double* val_thr, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- YIN F0 extractor (pitch/core/yin.py, libf0's YIN: pYIN's front half without the threshold sweep and the HMM; the one extractor that
+ * reports an aperiodicity per frame, a continuous voicing measure).  Added under ABI 22: purely additive.  fp64 throughout (the clip is
+ * fp32 and widens exactly).  Per frame the CMNDF over the lags 0 .. lag_max -- pYIN's kernel, the same bits --, the first strict local
+ * minimum below the threshold with its parabolic refinement, a second search inside +/- 25 cents of it, f0 = fs / lag, and the
+ * aperiodicity of the frame at that lag.  The device reproduces the reference as it executes under numpy.  The plan is
+ * plain data made by the host (svcmi/pitch/core/yin.py yin_plan): it holds no pointer. */
+typedef struct svcmi_yin_plan {
+    int32_t n_fft, hop, lag_min, lag_max;           /* frame length (even), hop, max(ceil(fs / f_max), 1), ceil(fs / f_min) <= n_fft */
+    double fs, threshold;                           /* sampling rate; the absolute threshold on the CMNDF (+inf is allowed: every minimum qualifies) */
+    double ratio_up, ratio_down;                    /* 2^(25 / 1200), 2^(-25 / 1200): the refinement window's two factors as the host computes them */
+} svcmi_yin_plan;
+int64_t svcmi_yin_plan_bytes(void);                 /* sizeof(svcmi_yin_plan), for a binding's layout check */
+#define SVCMI_YIN_MAX_NFFT 4096                     /* lag_max <= n_fft <= this */
+
+/* The kernels (csrc/yin.hip).  frames = 1 + n / hop for a clip of n samples; one frame is enough.
+ *   yin_cmndf:        x [n] fp32 -> cmndf [frames][lag_max + 1], bit for bit the rows of svcmi_pyin_cmndf_f64 at p_max = lag_max (it is that
+ *                     kernel), and rms [frames], which the kernel writes as well (YIN does not use it).
+ *   yin_pick:         cmndf rows -> lag [frames]; f0 = fs / lag, lag_first (the first search's result) and kind int32 [frames] may be NULL.
+ *                     A search over [lo, hi): lo == hi gives lo; else the first i in [lo, hi) with c[i] < c[i - 1], c[i] < c[i + 1] and
+ *                     c[i] < threshold, moved by -b / (2 a), a = eps + (y1 + y3 - 2 y2) / 2, b = (y3 - y1) / 2, eps = 2^-52, and c[i] replaced
+ *                     by y2 - b^2 / (4 a) in the kernel's copy of the row; else the lowest index of the smallest c[lo .. hi - 1], an
+ *                     integer.  First over [lag_min, lag_max) with the plan's threshold; then with threshold = +inf over
+ *                     [rint(fs / ((fs / lag) ratio_up)), rint(fs / ((fs / lag) ratio_down))), half to even, clipped to lag_min .. lag_max.
+ *                     kind: 1 = the first search took the lowest-value branch, 2 = the second returned its lower limit because the window
+ *                     was empty, 4 = the second took the lowest-value branch.  The rows are not modified.  They must not hold NaN or inf.
+ *   yin_aperiodicity: x, lag [frames] -> ap [frames] = res / (pwr + eps): with f the frame, g = (f, f reversed) and s[j] = g[L + j]
+ *                     (L = floor(lag); a lag without fractional part) or (1 - frac) g[L + j] + frac g[L + 1 + j], pwr = (mean f^2 +
+ *                     mean s^2) / 2, res = mean (f - s)^2 / 2.  The three sums in one fixed order per frame: the bits depend on the
+ *                     frame's samples and the lag alone.  Silence gives exactly 0.  0 <= lag <= n_fft, a fractional one < n_fft; the
+ *                     kernel reads nothing outside the frame whatever the lag holds.
+ * SVCMI_EINVAL before anything is launched for a null pointer (the optional outputs excepted), n < 1, frames < 1 or frames != 1 + n / hop,
+ * hop < 1, an odd n_fft (or < 2), lag_min < 1, lag_max < lag_min, fs <= 0, a NaN threshold, a ratio <= 0; SVCMI_EUNSUPPORTED for n_fft above
+ * the limit, lag_max > n_fft, frames >= 2^31 / (lag_max + 1); SVCMI_EALIGN for a pointer that is not aligned to its element. */
+int svcmi_yin_cmndf_f64(const svcmi_yin_plan* p, const float* x, int64_t n, double* cmndf, double* rms, int64_t frames, void* stream);
+int svcmi_yin_pick_f64(const svcmi_yin_plan* p, const double* cmndf, int64_t frames, double* lag, double* f0, double* lag_first, int32_t* kind,
+                       void* stream);
+int svcmi_yin_aperiodicity_f64(const svcmi_yin_plan* p, const float* x, int64_t n, const double* lag, int64_t frames, double* ap, void* stream);
+/* clip -> f0, ap [frames] float64 as ONE stage call: three launches on one workspace (the CMNDF rows, the rms the first kernel writes, and
+ * lag when the caller passes NULL for it), nothing waits.  lag, lag_first float64 [frames] and kind int32 [frames] may be NULL.
+ * SVCMI_EINVAL also for a workspace that is too small or not 256-byte aligned; the query returns a negative code for a geometry the
+ * stage would refuse. */
+int64_t svcmi_yin_workspace_bytes(const svcmi_yin_plan* p, int64_t n);
+int svcmi_yin_f0_fwd(const svcmi_yin_plan* p, const float* x, int64_t n, double* f0, double* ap, double* lag, double* lag_first, int32_t* kind,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- SWIPE' F0 extractor (pitch/core/swipe_slim.py, libf0's swipe_slim: the spectral one of the network-free extractors; it reports a
  * pitch strength per frame).  Added under ABI 22: purely additive.  Per window size N (a power of two, hop N / 2) the magnitudes of a
  * centred Hann STFT are resampled onto n_log log-frequency bins by a cubic spline -- a fixed linear map W_N the host tabulates --, every

@@ -16,6 +16,7 @@
 #include "../../include/svcmi.h"
 
 extern "C" int svcmi_pyin_plan_check_(const svcmi_pyin_plan* p);      // csrc/pyin.hip: the plan's own checks, for the planning pass
+extern "C" int svcmi_yin_plan_check_(const svcmi_yin_plan* p);        // csrc/yin.hip: likewise
 
 namespace {
 
@@ -30,6 +31,7 @@ enum Op {
     OP_COUPLING_PRE, OP_COUPLING_POST, OP_EMBED_PITCH, OP_SAMPLE_PRIOR, OP_NCL_TO_NLC, OP_COPY2D, OP_PITCH_PREFIX, OP_PITCH_SOURCE,
     OP_ATTENTION16, OP_SNAKE_CONV_GROUP_LP, OP_LSTM_STEP, OP_L2NORM_ROWS, OP_VAD_FRONTEND, OP_VAD_LSTM_SCAN,
     OP_SALIENCE_STFT, OP_SALIENCE_MAP, OP_SALIENCE_DP, OP_PYIN_CMNDF, OP_PYIN_OBSERVE, OP_PYIN_VITERBI, OP_PYIN_FINISH,
+    OP_YIN_CMNDF, OP_YIN_PICK, OP_YIN_APERIODICITY,
     OP_COUNT
 };
 const char* const OP_NAMES[OP_COUNT] = {
@@ -40,7 +42,8 @@ const char* const OP_NAMES[OP_COUNT] = {
     "svcmi_copy2d_f32", "svcmi_pitch_prefix_f64", "svcmi_pitch_source_f32", "svcmi_attention16", "svcmi_snake_conv_group_lp",
     "svcmi_lstm_step_f32", "svcmi_l2norm_rows_f32", "svcmi_vad_frontend_f32", "svcmi_vad_lstm_scan_f32",
     "svcmi_salience_stft_f32", "svcmi_salience_map_f32", "svcmi_salience_dp_f64",
-    "svcmi_pyin_cmndf_f64", "svcmi_pyin_observe_f64", "svcmi_pyin_viterbi_f64", "svcmi_pyin_finish_f64"};
+    "svcmi_pyin_cmndf_f64", "svcmi_pyin_observe_f64", "svcmi_pyin_viterbi_f64", "svcmi_pyin_finish_f64",
+    "svcmi_yin_cmndf_f64", "svcmi_yin_pick_f64", "svcmi_yin_aperiodicity_f64"};
 
 // ------------------------------------------------------------------------------------------------ per-launch trace (bench.py)
 struct TraceRec {
@@ -980,6 +983,28 @@ void pyin_fwd(Ctx& c, const svcmi_pyin_plan& p, const float* x, int64_t n, doubl
     run(c, OP_PYIN_FINISH, cells, 8.0 * cells, [&] { return svcmi_pyin_finish_f64(&p, path, o, r, lt, vt, frames, f0, conf, c.stream); });
 }
 
+// ------------------------------------------------------------------------------------------------ YIN F0 extractor
+// pitch/core/yin.py: clip -> f0, ap in three launches (csrc/yin.hip): the CMNDF rows (pYIN's kernel), the two thresholdings, the aperiodicity
+// at the lag they found.  lag may be the caller's buffer or NULL (then it lives in the workspace); lag_first and kind are optional outputs.
+void yin_fwd(Ctx& c, const svcmi_yin_plan& p, const float* x, int64_t n, double* f0, double* ap, double* lag, double* lag_first, int32_t* kind) {
+    if (int rc = svcmi_yin_plan_check_(&p)) { c.rc = rc; return; }
+    if (n < 1) { c.rc = SVCMI_EINVAL; return; }
+    const int64_t frames = 1 + n / p.hop, row = (int64_t)p.lag_max + 1;
+    if (frames >= 0x7fffffffLL / row) { c.rc = SVCMI_EUNSUPPORTED; return; }
+    auto f64 = [&](int64_t count) { return static_cast<double*>(c.ar.take(count * 8)); };
+    double* cm = f64(frames * row);
+    double* rms = f64(frames);
+    double* lg = lag ? lag : f64(frames);
+    const double cells = (double)frames * row;
+    run(c, OP_YIN_CMNDF, 3.0 * frames * p.lag_max * p.n_fft, 4.0 * n + 8.0 * cells, [&] {
+        return svcmi_yin_cmndf_f64(&p, x, n, cm, rms, frames, c.stream);
+    });
+    run(c, OP_YIN_PICK, 8.0 * cells, 8.0 * cells, [&] { return svcmi_yin_pick_f64(&p, cm, frames, lg, f0, lag_first, kind, c.stream); });
+    run(c, OP_YIN_APERIODICITY, 10.0 * frames * p.n_fft, 4.0 * n + 16.0 * frames, [&] {
+        return svcmi_yin_aperiodicity_f64(&p, x, n, lg, frames, ap, c.stream);
+    });
+}
+
 Ctx make_ctx(void* ws, int64_t bytes, void* stream, bool plan) {
     Ctx c;
     c.stream = stream;
@@ -1078,6 +1103,25 @@ extern "C" int svcmi_pyin_f0_fwd(const svcmi_pyin_plan* p, const float* x, int64
         return SVCMI_EALIGN;
     Ctx c = make_ctx(workspace, workspace_bytes, stream, false);
     pyin_fwd(c, *p, x, n, f0, conf, path, rms, O, lag_thr, val_thr);
+    return finish(c);
+}
+
+extern "C" int64_t svcmi_yin_workspace_bytes(const svcmi_yin_plan* p, int64_t n) {
+    if (!p) return SVCMI_EINVAL;
+    Ctx c = make_ctx(nullptr, 0, nullptr, true);
+    yin_fwd(c, *p, nullptr, n, nullptr, nullptr, nullptr, nullptr, nullptr);
+    return c.rc ? (int64_t)c.rc : c.ar.peak + 256;
+}
+
+extern "C" int svcmi_yin_f0_fwd(const svcmi_yin_plan* p, const float* x, int64_t n, double* f0, double* ap, double* lag, double* lag_first,
+                                int32_t* kind, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!p || !x || !f0 || !ap || !workspace) return SVCMI_EINVAL;
+    const int64_t need = svcmi_yin_workspace_bytes(p, n);
+    if (need < 0) return (int)need;
+    if (((uintptr_t)workspace & 255) || workspace_bytes < need) return SVCMI_EINVAL;
+    if (((uintptr_t)x & 3) || ((uintptr_t)kind & 3) || (((uintptr_t)f0 | (uintptr_t)ap | (uintptr_t)lag | (uintptr_t)lag_first) & 7)) return SVCMI_EALIGN;
+    Ctx c = make_ctx(workspace, workspace_bytes, stream, false);
+    yin_fwd(c, *p, x, n, f0, ap, lag, lag_first, kind);
     return finish(c);
 }
 

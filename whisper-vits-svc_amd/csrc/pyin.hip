@@ -429,6 +429,15 @@ extern "C" int64_t svcmi_pyin_plan_bytes(void) { return (int64_t)sizeof(svcmi_py
 // for the stage's planning pass (csrc/host_stages.hip): not part of the ABI
 extern "C" int svcmi_pyin_plan_check_(const svcmi_pyin_plan* p) { return plan_check(p); }
 
+// pyin_cmndf_kernel for csrc/yin.hip, whose rows must hold the same bits: the launch alone, for arguments the caller has checked (n_fft even,
+// 2 .. SVCMI_PYIN_MAX_NFFT; 1 <= p_max <= n_fft; frames = 1 + n / hop >= 1, any number: the kernel knows no frame but its own).  Not part
+// of the ABI
+extern "C" int svcmi_pyin_cmndf_launch_(const float* x, int64_t n, int32_t n_fft, int32_t hop, int32_t p_max, double* cmndf, double* rms,
+                                        int64_t frames, void* stream) {
+    SVCMI_LAUNCH(pyin_cmndf_kernel, dim3((unsigned)frames), dim3(PY_TPB), 0, stream, x, (long long)n, n_fft, hop, p_max, cmndf, rms);
+    return SVCMI_LAST_ERROR();
+}
+
 extern "C" int svcmi_pyin_cmndf_f64(const svcmi_pyin_plan* p, const float* x, int64_t n, double* cmndf, double* rms, int64_t frames, void* stream) {
     if (int rc = plan_check(p)) return rc;
     if (!x || !cmndf || !rms || n < 1 || frames != 1 + n / p->hop) return SVCMI_EINVAL;

@@ -214,6 +214,15 @@ class PyinPlan(Structure):
 PYIN_MAX_BINS, PYIN_MAX_THRESHOLDS, PYIN_MAX_NFFT, PYIN_MAX_BAND = 1024, 128, 4096, 33      # SVCMI_PYIN_MAX_*
 
 
+class YinPlan(Structure):
+    """svcmi_yin_plan"""
+    _fields_ = [("n_fft", c_int32), ("hop", c_int32), ("lag_min", c_int32), ("lag_max", c_int32),
+                ("fs", c_double), ("threshold", c_double), ("ratio_up", c_double), ("ratio_down", c_double)]
+
+
+YIN_MAX_NFFT = 4096                # SVCMI_YIN_MAX_NFFT
+
+
 class SwipeWindow(Structure):
     """svcmi_swipe_window"""
     _fields_ = [("basis", c_void_p), ("resample", c_void_p), ("kernels", c_void_p), ("cand", c_void_p), ("mu", c_void_p),
@@ -302,6 +311,12 @@ SIGNATURES = {
     "svcmi_pyin_finish_f64": (c_int, [POINTER(PyinPlan), _P, _P, _P, _P, _P, _L, _P, _P, _P]),
     "svcmi_pyin_workspace_bytes": (c_int64, [POINTER(PyinPlan), _L]),
     "svcmi_pyin_f0_fwd": (c_int, [POINTER(PyinPlan), _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "svcmi_yin_plan_bytes": (c_int64, []),
+    "svcmi_yin_cmndf_f64": (c_int, [POINTER(YinPlan), _P, _L, _P, _P, _L, _P]),
+    "svcmi_yin_pick_f64": (c_int, [POINTER(YinPlan), _P, _L, _P, _P, _P, _P, _P]),
+    "svcmi_yin_aperiodicity_f64": (c_int, [POINTER(YinPlan), _P, _L, _P, _L, _P, _P]),
+    "svcmi_yin_workspace_bytes": (c_int64, [POINTER(YinPlan), _L]),
+    "svcmi_yin_f0_fwd": (c_int, [POINTER(YinPlan), _P, _L, _P, _P, _P, _P, _P, _P, _L, _P]),
     "svcmi_swipe_plan_bytes": (c_int64, []),
     "svcmi_swipe_frames": (c_int64, [POINTER(SwipePlan), _I, _L]),
     "svcmi_swipe_mag_f32": (c_int, [POINTER(SwipePlan), _I, _P, _L, _P, _P]),
@@ -378,6 +393,8 @@ def load_library(path=None):
         raise SvcmiError(f"struct layout mismatch: svcmi_salience_plan is {lib.svcmi_salience_plan_bytes()} bytes in the library, {_c.sizeof(SaliencePlan)} in the binding")
     if lib.svcmi_pyin_plan_bytes() != _c.sizeof(PyinPlan):
         raise SvcmiError(f"struct layout mismatch: svcmi_pyin_plan is {lib.svcmi_pyin_plan_bytes()} bytes in the library, {_c.sizeof(PyinPlan)} in the binding")
+    if lib.svcmi_yin_plan_bytes() != _c.sizeof(YinPlan):
+        raise SvcmiError(f"struct layout mismatch: svcmi_yin_plan is {lib.svcmi_yin_plan_bytes()} bytes in the library, {_c.sizeof(YinPlan)} in the binding")
     if lib.svcmi_swipe_plan_bytes() != _c.sizeof(SwipePlan):
         raise SvcmiError(f"struct layout mismatch: svcmi_swipe_plan is {lib.svcmi_swipe_plan_bytes()} bytes in the library, {_c.sizeof(SwipePlan)} in the binding")
     return lib

@@ -1016,6 +1016,65 @@ class Ops:
                          _ptr(parts.get("O")), _ptr(parts.get("lag_thr")), _ptr(parts.get("val_thr")), ws, ws_bytes, self._stream())
         return (out, path, parts) if want_parts else (out, path)
 
+    # ------------------------------------------------------------------ YIN F0 extractor (csrc/yin.hip)
+    @staticmethod
+    def _yin_clip(name, plan, x):
+        if not (x.dim() == 1 and x.dtype == torch.float32 and x.shape[0] >= 1 and (x.shape[0] <= 1 or x.stride(0) == 1)):
+            raise SvcmiError(f"{name}: x must be float32 [n >= 1] with unit stride")
+        return 1 + int(x.shape[0]) // int(plan.hop)
+
+    def yin_cmndf(self, plan, x):
+        """x float32 [n] (unit stride) -> cmndf float64 [frames, lag_max + 1], frames = 1 + n // hop >= 1: the rows of ``pyin_cmndf`` at
+        p_max = lag_max, bit for bit (svcmi_yin_cmndf_f64).  ``plan``: the ``struct`` of ``svcmi.pitch.core.yin.yin_plan``."""
+        self._chk(x)
+        frames = self._yin_clip("yin_cmndf", plan, x)
+        cm = torch.empty(frames, plan.lag_max + 1, dtype=torch.float64, device=x.device)
+        rms = torch.empty(frames, dtype=torch.float64, device=x.device)      # the shared kernel writes it; YIN has no use for it
+        self._call("svcmi_yin_cmndf_f64", ctypes.byref(plan), _ptr(x), x.shape[0], _ptr(cm), _ptr(rms), frames, self._stream(),
+                   work={"flops": 3.0 * frames * plan.lag_max * plan.n_fft})
+        return cm
+
+    def yin_pick(self, plan, cmndf, want_parts=False):
+        """cmndf float64 [frames, lag_max + 1] (no NaN, no inf; not modified) -> out float64 [2, frames] (lag, f0 = fs / lag): the two
+        thresholdings of svcmi_yin_pick_f64; ``want_parts``: also (lag_first float64 [frames], kind int32 [frames])."""
+        self._chk(cmndf)
+        if not (cmndf.dim() == 2 and cmndf.dtype == torch.float64 and cmndf.is_contiguous() and cmndf.shape[1] == plan.lag_max + 1 and cmndf.shape[0] >= 1):
+            raise SvcmiError("yin_pick: cmndf must be a contiguous float64 [frames, lag_max + 1] tensor")
+        frames = cmndf.shape[0]
+        out = torch.empty(2, frames, dtype=torch.float64, device=cmndf.device)
+        first = torch.empty(frames, dtype=torch.float64, device=cmndf.device) if want_parts else None
+        kind = torch.empty(frames, dtype=torch.int32, device=cmndf.device) if want_parts else None
+        self._call("svcmi_yin_pick_f64", ctypes.byref(plan), _ptr(cmndf), frames, _ptr(out[0]), _ptr(out[1]), _ptr(first), _ptr(kind), self._stream())
+        return (out, first, kind) if want_parts else out
+
+    def yin_aperiodicity(self, plan, x, lag):
+        """x float32 [n] (unit stride), lag float64 [1 + n // hop] (0 <= lag <= n_fft, a fractional one < n_fft) -> ap float64 [frames]
+        (svcmi_yin_aperiodicity_f64)."""
+        self._chk(x)
+        self._chk(lag)
+        frames = self._yin_clip("yin_aperiodicity", plan, x)
+        if not (lag.dim() == 1 and lag.dtype == torch.float64 and lag.is_contiguous() and lag.shape[0] == frames):
+            raise SvcmiError(f"yin_aperiodicity: lag must be a contiguous float64 [{frames}] tensor")
+        ap = torch.empty(frames, dtype=torch.float64, device=x.device)
+        self._call("svcmi_yin_aperiodicity_f64", ctypes.byref(plan), _ptr(x), x.shape[0], _ptr(lag), frames, _ptr(ap), self._stream())
+        return ap
+
+    def yin_f0_fwd(self, plan, x, want_parts=False):
+        """clip float32 [n] -> out float64 [2, frames] (f0, ap) as ONE stage call (svcmi_yin_f0_fwd: three launches, nothing waits);
+        ``want_parts``: also a dict of lag, lag_first float64 [frames] and kind int32 [frames]."""
+        self._chk(x)
+        frames = self._yin_clip("yin_f0_fwd", plan, x)
+        need = self.lib.svcmi_yin_workspace_bytes(ctypes.byref(plan), x.shape[0])
+        if need < 0:
+            raise SvcmiError(f"svcmi_yin_workspace_bytes failed with code {need}")
+        ws, ws_bytes = self.stage_workspace(need, x.device)
+        new = lambda dtype: torch.empty(frames, dtype=dtype, device=x.device)
+        out = torch.empty(2, frames, dtype=torch.float64, device=x.device)
+        parts = dict(lag=new(torch.float64), lag_first=new(torch.float64), kind=new(torch.int32)) if want_parts else {}
+        self._stage_call("svcmi_yin_f0_fwd", ctypes.byref(plan), _ptr(x), x.shape[0], _ptr(out[0]), _ptr(out[1]), _ptr(parts.get("lag")),
+                         _ptr(parts.get("lag_first")), _ptr(parts.get("kind")), ws, ws_bytes, self._stream())
+        return (out, parts) if want_parts else out
+
     # ------------------------------------------------------------------ SWIPE' F0 extractor (csrc/swipe.hip)
     def _swipe_frames(self, plan, window, n):
         frames = self.lib.svcmi_swipe_frames(ctypes.byref(plan), int(window), int(n))

@@ -3,3 +3,4 @@ from .inference import Crepe, bins_to_hz, compute_f0_sing, compute_f0_train, dec
 from .inference import compute_f0_salience, compute_f0_salience_begin, move_average  # noqa: F401
 from .inference import compute_f0_pyin, compute_f0_pyin_begin  # noqa: F401
 from .inference import compute_f0_swipe, compute_f0_swipe_begin  # noqa: F401
+from .inference import compute_f0_yin, compute_f0_yin_begin  # noqa: F401

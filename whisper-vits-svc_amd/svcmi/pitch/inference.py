@@ -261,6 +261,38 @@ def compute_f0_pyin_begin(filename, device, ops=None):
     return finish
 
 
+def compute_f0_yin(filename, device, ap_threshold=None, ops=None):
+    """libf0's YIN (svcmi.pitch.core.yin at the parameters of ``compute_f0_salience``: Fs 16000, N 2048, H 320, 45 .. 1760 Hz, threshold
+    0.15) and the x2 repeat.  The reference has no such recipe; there is NO moving average, for ``compute_f0_pyin``'s reason.  YIN itself
+    decides no voicing: with ``ap_threshold`` None (libf0's behaviour) every frame is voiced, silence included; with a number, frames whose
+    aperiodicity is above it are 0.  ``filename``: wav path or a 16 kHz float waveform [n >= 1] (numpy, or a tensor on any device).
+    Returns np.float64 Hz [2 * (1 + n // 320)]."""
+    return compute_f0_yin_begin(filename, device, ap_threshold=ap_threshold, ops=ops)()
+
+
+@torch.no_grad()
+def compute_f0_yin_begin(filename, device, ap_threshold=None, ops=None):
+    """The device half of ``compute_f0_yin``, the contract of ``compute_f0_sing_begin``: difference function, thresholdings and
+    aperiodicity are ENQUEUED on the current stream and nothing waits; returns ``finish() -> np.float64 Hz`` which does the ONE
+    device -> host copy, the voicing decision and the repeat."""
+    from .core import yin as Y
+    if isinstance(filename, str):
+        from ..whisper.audio import load_audio
+        audio = torch.from_numpy(load_audio(filename))
+    else:
+        audio = torch.as_tensor(filename, dtype=torch.float32)
+    ops = ops if ops is not None else Y._default_ops()
+    plan = Y.yin_plan(Fs=SAMPLE_RATE, N=2048, H=320, F_min=45.0, F_max=1760.0, threshold=0.15)
+    done = Y.yin_begin(audio.to(device, torch.float32), plan, ops)
+
+    def finish():
+        f0, ap = done()
+        if ap_threshold is not None:
+            f0 = np.where(ap > ap_threshold, 0.0, f0)
+        return np.repeat(f0, 2, -1)                                       # 320 -> 160 * 2
+    return finish
+
+
 def compute_f0_swipe(filename, device, strength_threshold=0.0, ops=None):
     """libf0's SWIPE' (svcmi.pitch.core.swipe_slim at the parameters of ``compute_f0_salience``: Fs 16000, H 320, 45 .. 1760 Hz) and the x2
     repeat.  The reference has no such recipe.  ``edge="clamp"``: a frame whose arg-max is the last candidate takes that candidate's
