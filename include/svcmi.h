@@ -999,6 +999,49 @@ int svcmi_generator_fwd(const svcmi_synth_model* m, const svcmi_synth_io* io, co
 /* SynthesizerInfer.inference (vits/models.py:251-256): the three stages above on one workspace */
 int svcmi_synth_infer_fwd(const svcmi_synth_model* m, const svcmi_synth_io* io, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Key sweep (svc_inference_shift.py: one clip rendered at every transposition of a range).  Across keys only the pitch changes, so the
+ * two front convolutions of the prior encoder run once at batch 1 and everything behind the pitch embedding is an equal-length batch
+ * over the keys.  Added under ABI 22: new symbols only, no existing struct or entry point changes.
+ *   svcmi_sweep_pitch_f32  pit_k[k][t] = (float)((double)pit[t] * factors[k]) -- the reference's `np.array(pit) * 2 ** (shift / 12)` in
+ *                          float64, then torch.FloatTensor.  `factors` is HOST memory (n_keys doubles): the values travel in the kernel
+ *                          arguments.  The caller computes them (2 ** (shift / 12)); the kernel calls no pow.
+ *   svcmi_sweep_embed_f32  x[k][t][:] = (xs[t][:] + emb[f0_to_coarse(pit_k[k][t])][:]) * (t < length[0]) with the arithmetic of
+ *                          svcmi_embed_pitch_f32 (same device function, same operation order: the same bits as that kernel on n_keys
+ *                          copies of xs).  xs [t][ldxs] is the masked sum of the two front convolutions; x [n_keys][t][ldx] dense over
+ *                          keys; emb [256][c]; length: one int32 on the device, NULL = t.
+ * SVCMI_EINVAL before anything is launched for a null pointer (length excepted), n_keys / t / c < 1, ldxs or ldx < c; SVCMI_EUNSUPPORTED
+ * for n_keys > SVCMI_SWEEP_MAX_KEYS; SVCMI_EALIGN for c / ldxs / ldx % 4, xs / x / emb not 16-byte aligned, another pointer not aligned
+ * to its element. */
+#define SVCMI_SWEEP_MAX_KEYS 32
+int svcmi_sweep_pitch_f32(const float* pit, const double* factors, float* pit_k, int32_t n_keys, int32_t t, void* stream);
+int svcmi_sweep_embed_f32(const float* xs, int32_t ldxs, const float* pit_k, const float* emb, const int32_t* length, float* x,
+                          int32_t ldx, int32_t n_keys, int32_t t, int32_t c, void* stream);
+
+/* The whole sweep of one chunk as ONE call: the front convolutions at batch 1 (the launches svcmi_synth_infer_fwd makes for one clip),
+ * the two kernels above, then attention encoder, projection, prior sample, reverse flow and generator exactly as svcmi_synth_infer_fwd
+ * runs them at batch = n_keys (shared host code).  spk and length are replicated into the workspace.  With n_keys = 1 and factor 1.0 the
+ * call makes the launches of svcmi_synth_infer_fwd at batch 1 (the embedding through svcmi_sweep_embed_f32) and gives its bits. */
+typedef struct svcmi_sweep_io {
+    /* inputs at batch 1, device pointers */
+    const float* ppg;        /* [t >> ppg_row_shift][ppg_dim] */
+    const float* vec;        /* [t][vec_dim] */
+    const float* pit;        /* [t] Hz, the untransposed track */
+    const float* spk;        /* [spk_dim] */
+    const int32_t* length;   /* [1] */
+    /* per key, device pointers */
+    const float* source;     /* [n_keys][t*hop] harmonic sources of the transposed tracks (svcmi_pitch2source_fwd at batch n_keys on pit_k) */
+    const float* noise;      /* [n_keys][inter][t] */
+    double factors[SVCMI_SWEEP_MAX_KEYS];      /* 2 ** (shift / 12) per key, plain data */
+    int32_t ppg_row_shift, t, n_keys, stream_frames;
+    /* outputs */
+    float* wave;             /* [n_keys][t*hop] */
+    float* pit_k;            /* optional [n_keys][t]: the transposed tracks (NULL = kept in the workspace) */
+} svcmi_sweep_io;
+int64_t svcmi_sweep_io_bytes(void);      /* sizeof(svcmi_sweep_io), for FFI bindings */
+/* negative (SVCMI_EINVAL; SVCMI_EUNSUPPORTED for n_keys > SVCMI_SWEEP_MAX_KEYS) for a geometry the stage would refuse */
+int64_t svcmi_synth_sweep_workspace_bytes(const svcmi_synth_model* m, int32_t n_keys, int32_t t, int32_t stream_frames);
+int svcmi_synth_sweep_fwd(const svcmi_synth_model* m, const svcmi_sweep_io* io, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* y[r][0:cols] = x[r][0:cols] for `rows` rows of leading dimensions ldy / ldx (floats): the strided device copies of the host
  * above (time tiles of the streaming decoder, optional z_p / z outputs) as a kernel, so that they are stream-ordered and graph-capturable. */
 int svcmi_copy2d_f32(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int64_t cols, void* stream);

@@ -31,7 +31,7 @@ enum Op {
     OP_COUPLING_PRE, OP_COUPLING_POST, OP_EMBED_PITCH, OP_SAMPLE_PRIOR, OP_NCL_TO_NLC, OP_COPY2D, OP_PITCH_PREFIX, OP_PITCH_SOURCE,
     OP_ATTENTION16, OP_SNAKE_CONV_GROUP_LP, OP_LSTM_STEP, OP_L2NORM_ROWS, OP_VAD_FRONTEND, OP_VAD_LSTM_SCAN,
     OP_SALIENCE_STFT, OP_SALIENCE_MAP, OP_SALIENCE_DP, OP_PYIN_CMNDF, OP_PYIN_OBSERVE, OP_PYIN_VITERBI, OP_PYIN_FINISH,
-    OP_YIN_CMNDF, OP_YIN_PICK, OP_YIN_APERIODICITY,
+    OP_YIN_CMNDF, OP_YIN_PICK, OP_YIN_APERIODICITY, OP_SWEEP_PITCH, OP_SWEEP_EMBED,
     OP_COUNT
 };
 const char* const OP_NAMES[OP_COUNT] = {
@@ -43,7 +43,7 @@ const char* const OP_NAMES[OP_COUNT] = {
     "svcmi_lstm_step_f32", "svcmi_l2norm_rows_f32", "svcmi_vad_frontend_f32", "svcmi_vad_lstm_scan_f32",
     "svcmi_salience_stft_f32", "svcmi_salience_map_f32", "svcmi_salience_dp_f64",
     "svcmi_pyin_cmndf_f64", "svcmi_pyin_observe_f64", "svcmi_pyin_viterbi_f64", "svcmi_pyin_finish_f64",
-    "svcmi_yin_cmndf_f64", "svcmi_yin_pick_f64", "svcmi_yin_aperiodicity_f64"};
+    "svcmi_yin_cmndf_f64", "svcmi_yin_pick_f64", "svcmi_yin_aperiodicity_f64", "svcmi_sweep_pitch_f32", "svcmi_sweep_embed_f32"};
 
 // ------------------------------------------------------------------------------------------------ per-launch trace (bench.py)
 struct TraceRec {
@@ -429,12 +429,10 @@ void whisper_fwd(Ctx& c, const svcmi_whisper_model& m, const float* mel, const f
 
 // ------------------------------------------------------------------------------------------------ prior encoder
 // TextEncoder.forward, vits/models.py:39-52 + attentions.Encoder.forward, attentions.py:60-72.  z_p: [B][T][inter]
-void prior_fwd(Ctx& c, const svcmi_synth_model& m, const svcmi_synth_io& io, float* z_p) {
-    const int B = io.batch, T = io.t, H = m.hidden, I = m.inter, sh = io.ppg_row_shift;
-    const int64_t mark = c.ar.mark();
-    c.prec = class_prec(m, SVCMI_CLASS_ENC);
-    float* xa = c.ar.f((int64_t)B * T * H);
-    float* xb = c.ar.f((int64_t)B * T * H);
+// The two front convolutions: xa = pre(ppg) * mask + hub(vec) * mask (models.py:44-46).  The only part of the encoder that does not see
+// the pitch: the key sweep runs it once at batch 1 for all keys.
+void prior_front(Ctx& c, const svcmi_synth_model& m, const svcmi_synth_io& io, float* xa) {
+    const int B = io.batch, T = io.t, H = m.hidden, sh = io.ppg_row_shift;
     const int ppg_rows = (T + (1 << sh) - 1) >> sh;
     {
         CV v; v.x = io.ppg; v.x_bs = io.ppg_bstride ? io.ppg_bstride : (int64_t)ppg_rows * m.ppg_dim; v.B = B; v.t_in = T; v.t_out = T;
@@ -448,8 +446,12 @@ void prior_fwd(Ctx& c, const svcmi_synth_model& m, const svcmi_synth_io& io, flo
         v.y = xa; v.y_bs = (int64_t)T * H; v.ldy = H;
         conv(c, v);
     }
-    run(c, OP_EMBED_PITCH, 0.0, 8.0 * B * T * H,
-        [&] { return svcmi_embed_pitch_f32(xa, H, io.pit, m.pit_emb, io.lengths, B, T, H, c.stream); });
+}
+
+// Everything behind the pitch embedding: attention encoder, projection, prior sample.  xa: the embedded input [B][T][H] (overwritten),
+// xb: a second buffer of that size.
+void prior_tail(Ctx& c, const svcmi_synth_model& m, const svcmi_synth_io& io, float* xa, float* xb, float* z_p) {
+    const int B = io.batch, T = io.t, H = m.hidden, I = m.inter;
     const float scale = 1.0f / sqrtf((float)(H / m.n_heads));
     const int F = m.enc[0].f1.n, kf = m.enc_ffn_kernel, pl = (kf - 1) / 2;
     const int f2_nk = (m.enc[0].f2.ldw + 31) / 32;                     // K-steps of the second FFN convolution
@@ -515,6 +517,18 @@ void prior_fwd(Ctx& c, const svcmi_synth_model& m, const svcmi_synth_io& io, flo
     }
     run(c, OP_SAMPLE_PRIOR, 0.0, 16.0 * B * T * I,
         [&] { return svcmi_sample_prior_f32(stats, 2 * I, io.noise, io.lengths, z_p, I, B, T, I, c.stream); });
+}
+
+void prior_fwd(Ctx& c, const svcmi_synth_model& m, const svcmi_synth_io& io, float* z_p) {
+    const int B = io.batch, T = io.t, H = m.hidden;
+    const int64_t mark = c.ar.mark();
+    c.prec = class_prec(m, SVCMI_CLASS_ENC);
+    float* xa = c.ar.f((int64_t)B * T * H);
+    float* xb = c.ar.f((int64_t)B * T * H);
+    prior_front(c, m, io, xa);
+    run(c, OP_EMBED_PITCH, 0.0, 8.0 * B * T * H,
+        [&] { return svcmi_embed_pitch_f32(xa, H, io.pit, m.pit_emb, io.lengths, B, T, H, c.stream); });
+    prior_tail(c, m, io, xa, xb, z_p);
     c.ar.release(mark);
 }
 
@@ -859,6 +873,63 @@ void synth_fwd(Ctx& c, const svcmi_synth_model& m, const svcmi_synth_io& io) {
     generator_fwd(c, m, io, zp);
 }
 
+// ------------------------------------------------------------------------------------------------ key sweep
+// One chunk at n_keys transpositions (svc_inference_shift.py:60-70 is a loop of whole conversions): the front convolutions once at
+// batch 1, the pitch fan-out (csrc/sweep.hip), then the stages of synth_fwd at batch = n_keys.
+// `rows` copies of src[0:n] behind one another, by doubling: 1 + ceil(log2 rows) launches of the copy kernel.
+void replicate(Ctx& c, const float* src, float* dst, int64_t n, int rows) {
+    copy2d(c, src, n, dst, n, 1, n);
+    for (int have = 1; have < rows; have *= 2) {
+        const int add = have < rows - have ? have : rows - have;
+        copy2d(c, dst, add * n, dst + have * n, add * n, 1, add * n);
+    }
+}
+
+// the batch-1 and batch-n_keys views of a sweep: what synth_shapes_ok and the shared stages read
+void sweep_ios(const svcmi_sweep_io& io, svcmi_synth_io& one, svcmi_synth_io& all) {
+    memset(&one, 0, sizeof(one));
+    one.ppg = io.ppg; one.vec = io.vec; one.pit = io.pit; one.spk = io.spk; one.lengths = io.length;
+    one.ppg_row_shift = io.ppg_row_shift; one.batch = 1; one.t = io.t; one.stream_frames = io.stream_frames;
+    all = one;
+    all.ppg = nullptr; all.vec = nullptr; all.pit = nullptr;
+    all.source = io.source; all.noise = io.noise; all.wave = io.wave; all.batch = io.n_keys;
+}
+
+void sweep_fwd(Ctx& c, const svcmi_synth_model& m, const svcmi_sweep_io& io) {
+    svcmi_synth_io one, all;
+    sweep_ios(io, one, all);
+    if (io.n_keys < 1 || io.n_keys > SVCMI_SWEEP_MAX_KEYS || !synth_shapes_ok(m, one) || !synth_shapes_ok(m, all)) { c.rc = SVCMI_EINVAL; return; }
+    const int K = io.n_keys, T = io.t, H = m.hidden, I = m.inter;
+    c.lp_min_flops = m.lp_min_flops > 0.f ? m.lp_min_flops : 1.5e9f;
+    c.sk_ws = c.ar.f(SPLITK_FLOATS);
+    float* zp = c.ar.f((int64_t)K * T * I);
+    float* pit_k = io.pit_k ? io.pit_k : c.ar.f((int64_t)K * T);
+    if (K > 1) {       // (one key reads the caller's own spk / length, as svcmi_synth_infer_fwd would)
+        float* spk_k = c.ar.f((int64_t)K * m.spk_dim);
+        float* len_k = c.ar.f(K);      // int32 lengths: the copy kernel moves 4-byte words untouched
+        replicate(c, io.spk, spk_k, m.spk_dim, K);
+        replicate(c, reinterpret_cast<const float*>(io.length), len_k, 1, K);
+        all.spk = spk_k;
+        all.lengths = reinterpret_cast<const int32_t*>(len_k);
+    }
+    all.pit = pit_k;
+    {
+        const int64_t mark = c.ar.mark();
+        c.prec = class_prec(m, SVCMI_CLASS_ENC);
+        float* xa = c.ar.f((int64_t)K * T * H);
+        float* xb = c.ar.f((int64_t)K * T * H);
+        float* xs = K > 1 ? c.ar.f((int64_t)T * H) : xb;      // (xb is free until the encoder's first LayerNorm writes it)
+        prior_front(c, m, one, xs);
+        run(c, OP_SWEEP_PITCH, 0.0, 4.0 * T * (1 + K), [&] { return svcmi_sweep_pitch_f32(io.pit, io.factors, pit_k, K, T, c.stream); });
+        run(c, OP_SWEEP_EMBED, 0.0, 4.0 * T * H * (1.0 + K),
+            [&] { return svcmi_sweep_embed_f32(xs, H, pit_k, m.pit_emb, io.length, xa, H, K, T, H, c.stream); });
+        prior_tail(c, m, all, xa, xb, zp);
+        c.ar.release(mark);
+    }
+    flow_fwd(c, m, all, zp);
+    generator_fwd(c, m, all, zp);
+}
+
 // ------------------------------------------------------------------------------------------------ LSTM speaker encoder
 // speaker/models/lstm.py:35-71.  Per layer: Gx = X W_ih^T + (b_ih + b_hh) for all T steps in one GEMM (its columns already in the
 // step kernel's tile order: the weights were permuted at load), T step launches, then the projection GEMM -- of the whole sequence
@@ -1193,6 +1264,31 @@ extern "C" int svcmi_generator_fwd(const svcmi_synth_model* m, const svcmi_synth
 extern "C" int svcmi_synth_infer_fwd(const svcmi_synth_model* m, const svcmi_synth_io* io, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!io || !io->ppg || !io->vec || !io->pit || !io->spk || !io->lengths || !io->source || !io->noise || !io->wave) return SVCMI_EINVAL;
     return synth_entry(m, io, workspace, workspace_bytes, stream, [&](Ctx& c) { synth_fwd(c, *m, *io); });
+}
+
+extern "C" int64_t svcmi_sweep_io_bytes(void) { return (int64_t)sizeof(svcmi_sweep_io); }
+
+extern "C" int64_t svcmi_synth_sweep_workspace_bytes(const svcmi_synth_model* m, int32_t n_keys, int32_t t, int32_t stream_frames) {
+    if (!m || n_keys < 1 || t < 1) return SVCMI_EINVAL;
+    if (n_keys > SVCMI_SWEEP_MAX_KEYS) return SVCMI_EUNSUPPORTED;
+    svcmi_sweep_io io;
+    memset(&io, 0, sizeof(io));
+    io.n_keys = n_keys; io.t = t; io.stream_frames = stream_frames;
+    Ctx c = make_ctx(nullptr, 0, nullptr, true);
+    sweep_fwd(c, *m, io);
+    return c.rc ? (int64_t)c.rc : c.ar.peak + 256;
+}
+
+extern "C" int svcmi_synth_sweep_fwd(const svcmi_synth_model* m, const svcmi_sweep_io* io, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!m || !io || !workspace || ((uintptr_t)workspace & 255)) return SVCMI_EINVAL;
+    if (!io->ppg || !io->vec || !io->pit || !io->spk || !io->length || !io->source || !io->noise || !io->wave) return SVCMI_EINVAL;
+    if (io->n_keys > SVCMI_SWEEP_MAX_KEYS) return SVCMI_EUNSUPPORTED;
+    const int64_t need = svcmi_synth_sweep_workspace_bytes(m, io->n_keys, io->t, io->stream_frames);
+    if (need < 0) return (int)need;
+    if (workspace_bytes < need) return SVCMI_EINVAL;
+    Ctx c = make_ctx(workspace, workspace_bytes, stream, false);
+    sweep_fwd(c, *m, *io);
+    return finish(c);
 }
 
 extern "C" int svcmi_trace_begin(int32_t max_records) {

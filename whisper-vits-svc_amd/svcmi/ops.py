@@ -293,6 +293,71 @@ class Ops:
                          self._stream())
         return wave, z_p, z
 
+    # ------------------------------------------------------------------ key sweep (csrc/sweep.hip, svcmi_synth_sweep_fwd)
+    @staticmethod
+    def _factors(factors):
+        """The transposition factors as the C array the entry points read (host memory, doubles)."""
+        f = [float(v) for v in factors]
+        if not f:
+            raise SvcmiError("a key sweep needs at least one factor")
+        return (ctypes.c_double * len(f))(*f), len(f)
+
+    def sweep_pitch(self, pit, factors):
+        """pit [T] Hz, factors: K Python floats (2 ** (shift / 12)) -> pit_k [K, T] = float32(float64(pit) * factor): the reference's
+        ``np.array(pit) * 2 ** (shift / 12)`` followed by ``torch.FloatTensor``."""
+        self._chk(pit)
+        fac, K = self._factors(factors)
+        if pit.dim() != 1 or pit.dtype != torch.float32 or not pit.is_contiguous():
+            raise SvcmiError(f"expected a contiguous fp32 pitch track [T], got {tuple(pit.shape)} {pit.dtype}")
+        out = torch.empty(K, pit.shape[0], dtype=torch.float32, device=pit.device)
+        self._call("svcmi_sweep_pitch_f32", _ptr(pit), ctypes.addressof(fac), _ptr(out), K, pit.shape[0], self._stream())
+        return out
+
+    def sweep_embed(self, xs, pit_k, emb, length):
+        """xs [T, C] (the masked sum of the two front convolutions), pit_k [K, T], emb [256, C], length int32 [1] (or None) ->
+        x [K, T, C] = (xs + emb[f0_to_coarse(pit_k)]) * mask, the arithmetic of ``embed_pitch`` on K copies of xs."""
+        self._chk(xs, pit_k, emb, length)
+        K, T = pit_k.shape
+        C = xs.shape[1]
+        if tuple(xs.shape) != (T, C) or xs.stride(1) != 1 or not pit_k.is_contiguous() or tuple(emb.shape) != (256, C) or not emb.is_contiguous():
+            raise SvcmiError(f"sweep_embed: xs {tuple(xs.shape)}, pit_k {tuple(pit_k.shape)}, emb {tuple(emb.shape)} do not fit")
+        x = torch.empty(K, T, C, dtype=torch.float32, device=xs.device)
+        self._call("svcmi_sweep_embed_f32", _ptr(xs), xs.stride(0), _ptr(pit_k), _ptr(emb), _ptr(length), _ptr(x), C, K, T, C, self._stream())
+        return x
+
+    def synth_sweep_workspace_bytes(self, cm, n_keys, t, stream_frames=0):
+        return int(self.lib.svcmi_synth_sweep_workspace_bytes(ctypes.byref(cm.struct), int(n_keys), int(t), int(stream_frames)))
+
+    def synth_sweep_fwd(self, cm, ppg, vec, pit, spk, length, sources, noise, factors, *, ppg_row_shift=0, stream_frames=0, want_pit=False):
+        """One chunk at K transpositions as ONE call (svcmi_synth_sweep_fwd).  Batch-1 inputs: ppg [T >> shift, ppg_dim], vec [T, vec_dim],
+        pit [T], spk [spk_dim], length int32 [1]; per key: sources [K, T*hop], noise [K, inter, T], factors (K floats)
+        -> wave [K, 1, T*hop] (+ pit_k [K, T] with ``want_pit``)."""
+        self._chk(ppg, vec, pit, spk, length, sources, noise)
+        m = cm.struct
+        m.lp_min_flops = max(float(self.lp_min_flops), 1e-30)
+        fac, K = self._factors(factors)
+        T = pit.shape[0]
+        if K > _lib.SWEEP_MAX_KEYS:
+            raise SvcmiError(f"a key sweep takes at most {_lib.SWEEP_MAX_KEYS} keys per call, got {K}")
+        for t_, shape in ((ppg, ((T + (1 << ppg_row_shift) - 1) >> ppg_row_shift, m.ppg_dim)), (vec, (T, m.vec_dim)), (pit, (T,)), (spk, (m.spk_dim,)),
+                          (length, (1,)), (sources, (K, T * m.hop)), (noise, (K, m.inter, T))):
+            if tuple(t_.shape) != shape or not t_.is_contiguous():
+                raise SvcmiError(f"expected a contiguous tensor of shape {shape}, got {tuple(t_.shape)}")
+        need = self.lib.svcmi_synth_sweep_workspace_bytes(ctypes.byref(m), K, T, int(stream_frames))
+        if need < 0:
+            raise SvcmiError(f"svcmi_synth_sweep_workspace_bytes failed with code {need}")
+        ws, ws_bytes = self.stage_workspace(need, pit.device)
+        io = _lib.SweepIO()
+        io.ppg, io.vec, io.pit, io.spk, io.length, io.source, io.noise = (_ptr(t_) for t_ in (ppg, vec, pit, spk, length, sources, noise))
+        for i in range(K):
+            io.factors[i] = fac[i]
+        io.ppg_row_shift, io.t, io.n_keys, io.stream_frames = int(ppg_row_shift), T, K, int(stream_frames)
+        wave = torch.empty(K, 1, T * m.hop, dtype=torch.float32, device=pit.device)
+        pit_k = torch.empty(K, T, dtype=torch.float32, device=pit.device) if want_pit else None
+        io.wave, io.pit_k = _ptr(wave), _ptr(pit_k)
+        self._stage_call("svcmi_synth_sweep_fwd", ctypes.byref(m), ctypes.byref(io), ws, ws_bytes, self._stream())
+        return (wave, pit_k) if want_pit else wave
+
     def trace_begin(self, max_records=8192):
         """Per-launch timing of everything launched from here on (stage entry points: HIP events inside the C host; single-op calls of
         this class: torch events): bench.py's roofline leg."""

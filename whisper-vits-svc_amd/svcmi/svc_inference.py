@@ -140,6 +140,58 @@ def svc_infer(model, retrieval, spk, pit, ppg, vec, hp, device, noise=None, writ
     return out if return_tensor else out.cpu().numpy()
 
 
+SWEEP_KEY_BATCH = 16          # keys per stage call of svc_infer_sweep (profiles/key_sweep.md)
+
+
+@torch.no_grad()
+def svc_infer_sweep(model, retrieval, spk, pit, ppg, vec, hp, device, shifts, noise=None, key_batch=SWEEP_KEY_BATCH, return_tensor=False):
+    """The loop of svc_inference_shift.py:60-70 -- ``svc_infer`` on ``pit * 2 ** (shift / 12)`` for every shift -- as batches over the
+    keys.  Arguments as ``svc_infer``; ``pit`` is the untransposed track, ``shifts`` the semitone offsets.  Across keys only the pitch
+    changes: the feature copies, the retrieval blend and the prior encoder's two front convolutions happen once per chunk, the harmonic
+    sources come from one ``pitch2source`` at batch K, and everything behind the pitch embedding runs at batch ``key_batch`` (at most 32;
+    K keys go in groups of that size).  The chunk schedule is ``svc_infer``'s.  ``noise``: the dict of ``svc_infer`` with a leading key
+    axis on every entry (rand_ini [K,1,11], src_noise [K,1,L,11], enc_noises [[K,1,inter,len_i] per chunk]); without it every key draws
+    its own, as the reference's loop does.  Returns a list of K np.float32 [hop*T - 1] (device tensors with ``return_tensor``)."""
+    from ._lib import SWEEP_MAX_KEYS
+    shifts = list(shifts)
+    K, key_batch = len(shifts), int(key_batch)
+    if K < 1:
+        raise ValueError("svc_infer_sweep: no shifts given")
+    if not 1 <= key_batch <= SWEEP_MAX_KEYS:
+        raise ValueError(f"svc_infer_sweep: key_batch must be in 1..{SWEEP_MAX_KEYS}, got {key_batch}")
+    factors = [2 ** (s / 12) for s in shifts]              # float64, the reference's expression
+    dev = torch.device(device)
+    n = min(pit.shape[0], vec.shape[0], ppg.shape[0])
+    pit = pit[:n].to(dev, torch.float32).contiguous()
+    vec = vec[:n].to(dev, torch.float32)
+    ppg = ppg[:n].to(dev, torch.float32)
+    spk = spk.to(dev, torch.float32).unsqueeze(0)
+    hop = hp.data.hop_length
+    groups = [(g, min(g + key_batch, K)) for g in range(0, K, key_batch)]
+    pit_k = torch.cat([model.ops.sweep_pitch(pit, factors[a:b]) for a, b in groups])       # [K, n]: float32(float64(pit) * factor)
+    src_noise = None if noise is None else (noise["rand_ini"].reshape(K, -1), noise["src_noise"].reshape(K, n * hop, -1))
+    source = model.pitch2source(pit_k, noise=src_noise)                                    # [K, 1, hop * n]
+    retrieval = retrieval if retrieval is not None else DummyRetrieval()
+    passthrough = isinstance(retrieval, DummyRetrieval)
+    pieces = [[] for _ in range(K)]
+    for i, (cs, ce, cso, ceo) in enumerate(chunk_schedule(n, hop)):
+        sub_ppg, sub_vec = ppg[cs:ce], vec[cs:ce]
+        if getattr(retrieval, "on_device", False):
+            sub_ppg, sub_vec = retrieval.retriv_whisper(sub_ppg), retrieval.retriv_hubert(sub_vec)
+        elif not passthrough:
+            sub_ppg = retrieval.retriv_whisper(sub_ppg.cpu()).to(dev)
+            sub_vec = retrieval.retriv_hubert(sub_vec.cpu()).to(dev)
+        sub_len = torch.tensor([ce - cs], dtype=torch.int64)
+        enc_noise = None if noise is None else noise["enc_noises"][i].reshape(K, -1, ce - cs)
+        for a, b in groups:
+            sub_out = model.inference_sweep(sub_ppg.unsqueeze(0), sub_vec.unsqueeze(0), pit[cs:ce].unsqueeze(0), spk, sub_len,
+                                            source[a:b, :, cs * hop:ce * hop], factors[a:b], noise=None if enc_noise is None else enc_noise[a:b])
+            for k in range(a, b):
+                pieces[k].append(sub_out[k - a, 0, cso:ceo])
+    outs = [torch.cat(p) for p in pieces]
+    return outs if return_tensor else [o.cpu().numpy() for o in outs]
+
+
 F0_METHODS = ("crepe", "salience", "pyin")
 F0_CHOICES = F0_METHODS + ("swipe",)       # what --f0 and extract_features take (F0_METHODS keeps the value its users pin)
 

@@ -194,6 +194,25 @@ class SynthesizerInfer:
     __call__ = inference
 
     @torch.no_grad()
+    def inference_sweep(self, ppg, vec, pit, spk, ppg_l, sources, factors, noise=None):
+        """``inference`` of ONE clip at K transpositions (svc_inference_shift.py's loop over keys as a batch): ppg [1,T,ppg_dim],
+        vec [1,T,vec_dim], pit [1,T] Hz (untransposed), spk [1,spk_dim], ppg_l int64 [1], sources [K,1,hop*T] (``pitch2source`` of the K
+        transposed tracks), factors: K floats ``2 ** (shift / 12)`` -> waveforms [K,1,hop*T].  The two front convolutions run once; the
+        rest is the batch-K pipeline.  ``noise`` [K,inter,T]: the randn_like(m) of each key (default: fresh draws per key)."""
+        w, ops, dev = self._weights(), self.ops, self._device
+        factors = [float(f) for f in factors]
+        K, T = len(factors), ppg.shape[1]
+        if ppg.shape[0] != 1 or pit.shape[0] != 1:
+            raise ValueError("inference_sweep takes one clip (batch 1) and K factors")
+        ppg, vec, pit, spk = (t.to(dev, torch.float32).contiguous()[0] for t in (ppg, vec, pit, spk))
+        length = ppg_l.to(dev, torch.int32).contiguous().view(1)
+        sources = sources.to(dev, torch.float32).contiguous().view(K, T * w.hop)
+        if noise is None:
+            noise = torch.randn(K, w.I, T, device=dev)
+        noise = noise.to(dev, torch.float32).contiguous()
+        return ops.synth_sweep_fwd(self._cmodel(), ppg, vec, pit, spk, length, sources, noise, factors, stream_frames=self.stream_frames or 0)
+
+    @torch.no_grad()
     def inference_ppg50(self, ppg50, vec, pit, spk, lengths, source, noise=None):
         """Same as ``inference`` but takes the Whisper PPG at its native 50 fps ([B, ceil(T/2), ppg_dim], may be a batch-strided view of
         the encoder output) and fuses the ``np.repeat(ppg, 2, 0)`` of svc_inference.py:175-177 into the first conv's loads.  All
