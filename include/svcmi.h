@@ -1042,6 +1042,45 @@ int64_t svcmi_sweep_io_bytes(void);      /* sizeof(svcmi_sweep_io), for FFI bind
 int64_t svcmi_synth_sweep_workspace_bytes(const svcmi_synth_model* m, int32_t n_keys, int32_t t, int32_t stream_frames);
 int svcmi_synth_sweep_fwd(const svcmi_synth_model* m, const svcmi_sweep_io* io, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Singer sweep (svcmi.svc_inference_singers: one clip rendered in many timbres).  Across singers nothing up to and including the prior
+ * statistics sees the speaker, so the whole prior encoder runs once at batch 1; the speaker enters at the reverse flow and at the
+ * generator's SpeakerAdapter, which run as an equal-length batch over the singers.  Added under ABI 22: new symbols only.
+ *   svcmi_sweep_sample_prior_f32  z[r][t][:] = (m[t][:] + noise[r][:][t] * exp(logs[t][:])) * (t < length[0]) for n_rows noise draws on ONE
+ *                                 set of statistics.  stats [t][lds] holds m | logs at batch 1 (lds >= 2 i); noise_ncl [n_rows][i][t] in
+ *                                 the reference's randn_like(m) layout; z [n_rows][t][ldz] time-major; length: one int32 on the
+ *                                 device, NULL = t.  Row r holds exactly the bits svcmi_sample_prior_f32 writes on a copy of `stats`
+ *                                 with noise[r] (same device functions, csrc/prior_sample.h); exp is taken once per element, not per row.
+ * SVCMI_EINVAL before anything is launched for a null pointer (length excepted), n_rows / t / i < 1, lds < 2 i or ldz < i;
+ * SVCMI_EUNSUPPORTED for n_rows > SVCMI_SINGERS_MAX; SVCMI_EALIGN for a pointer not aligned to its element. */
+#define SVCMI_SINGERS_MAX 32
+int svcmi_sweep_sample_prior_f32(const float* stats, int32_t lds, const float* noise_ncl, const int32_t* length,
+                                 float* z, int32_t ldz, int32_t n_rows, int32_t t, int32_t i, void* stream);
+
+/* One chunk in n_singers timbres as ONE call: the front convolutions, the pitch embedding, the attention encoder and the projection at
+ * batch 1 (the launches svcmi_synth_infer_fwd makes for one clip), the kernel above into z_p [n_singers][t][inter], then reverse flow and
+ * generator exactly as svcmi_synth_infer_fwd runs them at batch = n_singers (shared host code) with the caller's spk rows.  The length and
+ * the ONE harmonic source are replicated into the workspace.  With n_singers = 1 the call makes the launches of svcmi_synth_infer_fwd at
+ * batch 1 (the sample through svcmi_sweep_sample_prior_f32) and gives its bits. */
+typedef struct svcmi_singers_io {
+    /* inputs at batch 1, device pointers */
+    const float* ppg;        /* [t >> ppg_row_shift][ppg_dim] */
+    const float* vec;        /* [t][vec_dim] */
+    const float* pit;        /* [t] Hz */
+    const int32_t* length;   /* [1] */
+    const float* source;     /* [t*hop]: ONE harmonic source, shared by all singers */
+    /* per singer, device pointers */
+    const float* spk;        /* [n_singers][spk_dim] */
+    const float* noise;      /* [n_singers][inter][t] */
+    int32_t ppg_row_shift, t, n_singers, stream_frames;
+    /* outputs */
+    float* wave;             /* [n_singers][t*hop] */
+    float* z_p;              /* optional [n_singers][t][inter] (NULL = skip) */
+} svcmi_singers_io;
+int64_t svcmi_singers_io_bytes(void);    /* sizeof(svcmi_singers_io), for FFI bindings */
+/* negative (SVCMI_EINVAL; SVCMI_EUNSUPPORTED for n_singers > SVCMI_SINGERS_MAX) for a geometry the stage would refuse */
+int64_t svcmi_synth_singers_workspace_bytes(const svcmi_synth_model* m, int32_t n_singers, int32_t t, int32_t stream_frames);
+int svcmi_synth_singers_fwd(const svcmi_synth_model* m, const svcmi_singers_io* io, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* y[r][0:cols] = x[r][0:cols] for `rows` rows of leading dimensions ldy / ldx (floats): the strided device copies of the host
  * above (time tiles of the streaming decoder, optional z_p / z outputs) as a kernel, so that they are stream-ordered and graph-capturable. */
 int svcmi_copy2d_f32(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int64_t cols, void* stream);

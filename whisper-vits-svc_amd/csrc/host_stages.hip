@@ -28,7 +28,7 @@ int g_amp_lp = 1;
 enum Op {
     OP_CONV_F32, OP_CONV_LP, OP_CONV_GROUP_F32, OP_CONV_GROUP_LP, OP_LAYERNORM, OP_SPLITK_LN, OP_ATTENTION, OP_SNAKE_ALIAS,
     OP_SNAKE_ALIAS_GROUP, OP_BLOCK_MEAN, OP_SNAKE_CONV, OP_SNAKE_CONV_GROUP, OP_UPSAMPLE_NOISE, OP_SNAKE_POST, OP_WN_GATE,
-    OP_COUPLING_PRE, OP_COUPLING_POST, OP_EMBED_PITCH, OP_SAMPLE_PRIOR, OP_NCL_TO_NLC, OP_COPY2D, OP_PITCH_PREFIX, OP_PITCH_SOURCE,
+    OP_COUPLING_PRE, OP_COUPLING_POST, OP_EMBED_PITCH, OP_SAMPLE_PRIOR, OP_SWEEP_SAMPLE_PRIOR, OP_NCL_TO_NLC, OP_COPY2D, OP_PITCH_PREFIX, OP_PITCH_SOURCE,
     OP_ATTENTION16, OP_SNAKE_CONV_GROUP_LP, OP_LSTM_STEP, OP_L2NORM_ROWS, OP_VAD_FRONTEND, OP_VAD_LSTM_SCAN,
     OP_SALIENCE_STFT, OP_SALIENCE_MAP, OP_SALIENCE_DP, OP_PYIN_CMNDF, OP_PYIN_OBSERVE, OP_PYIN_VITERBI, OP_PYIN_FINISH,
     OP_YIN_CMNDF, OP_YIN_PICK, OP_YIN_APERIODICITY, OP_SWEEP_PITCH, OP_SWEEP_EMBED,
@@ -38,7 +38,7 @@ const char* const OP_NAMES[OP_COUNT] = {
     "svcmi_conv_gemm_f32", "svcmi_conv_gemm_lp", "svcmi_conv_gemm_group_f32", "svcmi_conv_gemm_group_lp", "svcmi_layernorm_f32",
     "svcmi_splitk_layernorm_f32", "svcmi_attention_f32", "svcmi_snake_alias_f32", "svcmi_snake_alias_group_f32", "svcmi_block_mean_f32",
     "svcmi_snake_conv_f32", "svcmi_snake_conv_group_f32", "svcmi_upsample_noise_f32", "svcmi_snake_post_f32", "svcmi_wn_gate_f32",
-    "svcmi_coupling_pre_f32", "svcmi_coupling_post_f32", "svcmi_embed_pitch_f32", "svcmi_sample_prior_f32", "svcmi_ncl_to_nlc_f32",
+    "svcmi_coupling_pre_f32", "svcmi_coupling_post_f32", "svcmi_embed_pitch_f32", "svcmi_sample_prior_f32", "svcmi_sweep_sample_prior_f32", "svcmi_ncl_to_nlc_f32",
     "svcmi_copy2d_f32", "svcmi_pitch_prefix_f64", "svcmi_pitch_source_f32", "svcmi_attention16", "svcmi_snake_conv_group_lp",
     "svcmi_lstm_step_f32", "svcmi_l2norm_rows_f32", "svcmi_vad_frontend_f32", "svcmi_vad_lstm_scan_f32",
     "svcmi_salience_stft_f32", "svcmi_salience_map_f32", "svcmi_salience_dp_f64",
@@ -449,8 +449,9 @@ void prior_front(Ctx& c, const svcmi_synth_model& m, const svcmi_synth_io& io, f
 }
 
 // Everything behind the pitch embedding: attention encoder, projection, prior sample.  xa: the embedded input [B][T][H] (overwritten),
-// xb: a second buffer of that size.
-void prior_tail(Ctx& c, const svcmi_synth_model& m, const svcmi_synth_io& io, float* xa, float* xb, float* z_p) {
+// xb: a second buffer of that size.  With `stats_out` the function stops before the sample and hands out the projection's m | logs
+// ([B][T][2I], in the arena: valid until the caller releases its mark) -- the singer sweep draws from them once per singer.
+void prior_tail(Ctx& c, const svcmi_synth_model& m, const svcmi_synth_io& io, float* xa, float* xb, float* z_p, float** stats_out = nullptr) {
     const int B = io.batch, T = io.t, H = m.hidden, I = m.inter;
     const float scale = 1.0f / sqrtf((float)(H / m.n_heads));
     const int F = m.enc[0].f1.n, kf = m.enc_ffn_kernel, pl = (kf - 1) / 2;
@@ -515,6 +516,7 @@ void prior_tail(Ctx& c, const svcmi_synth_model& m, const svcmi_synth_io& io, fl
         v.mask_in = v.mask_out = true; v.y = stats; v.y_bs = (int64_t)T * 2 * I; v.ldy = 2 * I;
         conv(c, v);
     }
+    if (stats_out) { *stats_out = stats; return; }
     run(c, OP_SAMPLE_PRIOR, 0.0, 16.0 * B * T * I,
         [&] { return svcmi_sample_prior_f32(stats, 2 * I, io.noise, io.lengths, z_p, I, B, T, I, c.stream); });
 }
@@ -930,6 +932,53 @@ void sweep_fwd(Ctx& c, const svcmi_synth_model& m, const svcmi_sweep_io& io) {
     generator_fwd(c, m, all, zp);
 }
 
+// ------------------------------------------------------------------------------------------------ singer sweep
+// One chunk in n_singers timbres (svcmi.svc_inference_singers; the reference: a loop of whole svc_inference.py runs): nothing up to and
+// including the prior statistics reads the speaker, so the prior encoder runs once at batch 1, the statistics fan out to one noise draw
+// per singer (csrc/sweep.hip), and flow and generator -- where the speaker enters -- run at batch = n_singers with the caller's spk rows.
+void singers_ios(const svcmi_singers_io& io, svcmi_synth_io& one, svcmi_synth_io& all) {
+    memset(&one, 0, sizeof(one));
+    one.ppg = io.ppg; one.vec = io.vec; one.pit = io.pit; one.lengths = io.length;
+    one.ppg_row_shift = io.ppg_row_shift; one.batch = 1; one.t = io.t; one.stream_frames = io.stream_frames;
+    all = one;
+    all.ppg = nullptr; all.vec = nullptr; all.pit = nullptr;
+    all.spk = io.spk; all.source = io.source; all.wave = io.wave; all.batch = io.n_singers;
+}
+
+void singers_fwd(Ctx& c, const svcmi_synth_model& m, const svcmi_singers_io& io) {
+    svcmi_synth_io one, all;
+    singers_ios(io, one, all);
+    if (io.n_singers < 1 || io.n_singers > SVCMI_SINGERS_MAX || !synth_shapes_ok(m, one) || !synth_shapes_ok(m, all)) { c.rc = SVCMI_EINVAL; return; }
+    const int N = io.n_singers, T = io.t, H = m.hidden, I = m.inter;
+    c.lp_min_flops = m.lp_min_flops > 0.f ? m.lp_min_flops : 1.5e9f;
+    c.sk_ws = c.ar.f(SPLITK_FLOATS);
+    float* zp = c.ar.f((int64_t)N * T * I);
+    {
+        const int64_t mark = c.ar.mark();
+        c.prec = class_prec(m, SVCMI_CLASS_ENC);
+        float* xa = c.ar.f((int64_t)T * H);
+        float* xb = c.ar.f((int64_t)T * H);
+        float* stats = nullptr;
+        prior_front(c, m, one, xa);
+        run(c, OP_EMBED_PITCH, 0.0, 8.0 * T * H, [&] { return svcmi_embed_pitch_f32(xa, H, io.pit, m.pit_emb, io.length, 1, T, H, c.stream); });
+        prior_tail(c, m, one, xa, xb, nullptr, &stats);
+        run(c, OP_SWEEP_SAMPLE_PRIOR, 0.0, 4.0 * T * I * (2.0 + 2.0 * N),
+            [&] { return svcmi_sweep_sample_prior_f32(stats, 2 * I, io.noise, io.length, zp, I, N, T, I, c.stream); });
+        c.ar.release(mark);
+    }
+    if (io.z_p) copy2d(c, zp, (int64_t)T * I, io.z_p, (int64_t)T * I, N, (int64_t)T * I);
+    if (N > 1) {       // (one singer reads the caller's own length / source, as svcmi_synth_infer_fwd would)
+        float* len_n = c.ar.f(N);      // int32 lengths: the copy kernel moves 4-byte words untouched
+        float* src_n = c.ar.f((int64_t)N * T * m.hop);
+        replicate(c, reinterpret_cast<const float*>(io.length), len_n, 1, N);
+        replicate(c, io.source, src_n, (int64_t)T * m.hop, N);
+        all.lengths = reinterpret_cast<const int32_t*>(len_n);
+        all.source = src_n;
+    }
+    flow_fwd(c, m, all, zp);
+    generator_fwd(c, m, all, zp);
+}
+
 // ------------------------------------------------------------------------------------------------ LSTM speaker encoder
 // speaker/models/lstm.py:35-71.  Per layer: Gx = X W_ih^T + (b_ih + b_hh) for all T steps in one GEMM (its columns already in the
 // step kernel's tile order: the weights were permuted at load), T step launches, then the projection GEMM -- of the whole sequence
@@ -1288,6 +1337,31 @@ extern "C" int svcmi_synth_sweep_fwd(const svcmi_synth_model* m, const svcmi_swe
     if (workspace_bytes < need) return SVCMI_EINVAL;
     Ctx c = make_ctx(workspace, workspace_bytes, stream, false);
     sweep_fwd(c, *m, *io);
+    return finish(c);
+}
+
+extern "C" int64_t svcmi_singers_io_bytes(void) { return (int64_t)sizeof(svcmi_singers_io); }
+
+extern "C" int64_t svcmi_synth_singers_workspace_bytes(const svcmi_synth_model* m, int32_t n_singers, int32_t t, int32_t stream_frames) {
+    if (!m || n_singers < 1 || t < 1) return SVCMI_EINVAL;
+    if (n_singers > SVCMI_SINGERS_MAX) return SVCMI_EUNSUPPORTED;
+    svcmi_singers_io io;
+    memset(&io, 0, sizeof(io));
+    io.n_singers = n_singers; io.t = t; io.stream_frames = stream_frames;
+    Ctx c = make_ctx(nullptr, 0, nullptr, true);
+    singers_fwd(c, *m, io);
+    return c.rc ? (int64_t)c.rc : c.ar.peak + 256;
+}
+
+extern "C" int svcmi_synth_singers_fwd(const svcmi_synth_model* m, const svcmi_singers_io* io, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!m || !io || !workspace || ((uintptr_t)workspace & 255)) return SVCMI_EINVAL;
+    if (!io->ppg || !io->vec || !io->pit || !io->spk || !io->length || !io->source || !io->noise || !io->wave) return SVCMI_EINVAL;
+    if (io->n_singers > SVCMI_SINGERS_MAX) return SVCMI_EUNSUPPORTED;
+    const int64_t need = svcmi_synth_singers_workspace_bytes(m, io->n_singers, io->t, io->stream_frames);
+    if (need < 0) return (int)need;
+    if (workspace_bytes < need) return SVCMI_EINVAL;
+    Ctx c = make_ctx(workspace, workspace_bytes, stream, false);
+    singers_fwd(c, *m, *io);
     return finish(c);
 }
 

@@ -6,9 +6,20 @@
 // Both are one-pass streaming kernels like the rest of the prior encoder's glue (vits_elem.hip): float4 lanes, channel index fastest,
 // the key on blockIdx.y so that everything a block needs of its key (the factor, the row bases) is wave-uniform.  xs is read once per
 // key (T x H floats: resident in L2 after the first key), x is written once.
+//
+// The singer sweep (svcmi.svc_inference_singers: one clip in many timbres) shares more: nothing up to the prior statistics sees the
+// speaker, so the whole prior encoder runs once at batch 1 and ONE kernel fans its m | logs out to a noise draw per singer:
+//   sweep_sample_prior_kernel   z[r][t][:] = (m[t][:] + noise[r][:][t] * exp(logs[t][:])) * mask
+// the 32 x 32 LDS-transposed tile of sample_prior_kernel (vits_elem.hip) with the arithmetic of prior_sample.h.  A block keeps m and
+// exp(logs) of its tile in registers (4 + 4 per thread, one expf per element whatever the number of rows) and walks a contiguous group
+// of rows, each row's noise tile through a double-buffered [32][33] LDS transpose (one barrier per row).  Rows per block: the rows are
+// split over blockIdx.z into the fewest groups that bring the grid to 512 blocks (two per CU) or to one row per block, whichever comes
+// first -- at base widths one chunk is about 31 x 6 tiles, so 16 singers go as 3 groups of 6, 6 and 4 rows.  Glue: memory-bound,
+// microseconds; what the sweep saves is the S - 1 prior encoders that do not run.
 #include "svcmi_rt.h"
 #include "../../include/svcmi.h"
 #include "pitch_coarse.h"
+#include "prior_sample.h"
 
 namespace {
 
@@ -45,6 +56,40 @@ __global__ __launch_bounds__(TPB) void sweep_embed_kernel(const float* xs, int l
     }
 }
 
+__global__ __launch_bounds__(TPB) void sweep_sample_prior_kernel(const float* stats, int lds_, const float* noise, const int32_t* length,
+                                                                 float* z, int ldz, int n_rows, int rows_per_block, int t, int ic) {
+    __shared__ float tile[2][32][33];
+    const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+    const int r0 = blockIdx.z * rows_per_block, r1 = r0 + rows_per_block < n_rows ? r0 + rows_per_block : n_rows;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
+    const int len = length ? length[0] : t;
+    const int c = c0 + tx;
+    float m[4], e[4];                                           // the thread's four elements of the tile: stats[t0+ty+8j][c], once for all rows
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int tt = t0 + ty + 8 * j;
+        const bool in = tt < t && c < ic;
+        const float* sp = stats + (long long)tt * lds_;
+        m[j] = in ? sp[c] : 0.f;
+        e[j] = in ? prior_scale(sp[ic + c]) : 0.f;
+    }
+    for (int r = r0; r < r1; ++r) {
+        float(*tl)[33] = tile[(r - r0) & 1];                    // two buffers: the barrier of row r + 1 separates row r's reads from row r + 2's writes
+        const float* nb = noise + (long long)r * ic * t;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                           // noise[r][c0+k][t0+tx]
+            const int k = ty + 8 * j, cn = c0 + k, tn = t0 + tx;
+            tl[k][tx] = (cn < ic && tn < t) ? nb[(long long)cn * t + tn] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                           // z[r][t0+k][c0+tx]
+            const int k = ty + 8 * j, tt = t0 + k;
+            if (tt < t && c < ic) prior_sample_store(z + ((long long)r * t + tt) * ldz + c, m[j], tl[tx][k], e[j], tt < len);
+        }
+    }
+}
+
 inline unsigned blocks_for(long long total) {
     const long long nb = (total + TPB - 1) / TPB;
     const long long cap = 256 * 8;   // CUs x blocks/CU over all keys' rows at most, grid-stride beyond that
@@ -72,5 +117,23 @@ extern "C" int svcmi_sweep_embed_f32(const float* xs, int32_t ldxs, const float*
     if (c % 4 || ldxs % 4 || ldx % 4 || mis(xs, 16) || mis(x, 16) || mis(emb, 16) || mis(pit_k, 4) || mis(length, 4)) return SVCMI_EALIGN;
     SVCMI_LAUNCH(sweep_embed_kernel, dim3(blocks_for((long long)t * (c / 4)), n_keys), dim3(TPB), 0, stream, xs, ldxs, pit_k, emb, length, x,
                  ldx, t, c);
+    return SVCMI_LAST_ERROR();
+}
+
+extern "C" int svcmi_sweep_sample_prior_f32(const float* stats, int32_t lds, const float* noise_ncl, const int32_t* length, float* z,
+                                            int32_t ldz, int32_t n_rows, int32_t t, int32_t i, void* stream) {
+    if (!stats || !noise_ncl || !z || n_rows <= 0 || t <= 0 || i <= 0 || lds < 2 * i || ldz < i) return SVCMI_EINVAL;
+    if (n_rows > SVCMI_SINGERS_MAX) return SVCMI_EUNSUPPORTED;
+    if (mis(stats, 4) || mis(noise_ncl, 4) || mis(z, 4) || mis(length, 4)) return SVCMI_EALIGN;
+    const int gx = (t - 1) / 32 + 1, gy = (i - 1) / 32 + 1;
+    if (gy > 65535) return SVCMI_EUNSUPPORTED;
+    // the fewest row groups that bring the grid to 512 blocks, at most one group per row
+    const long long tiles = (long long)gx * gy;
+    long long groups = (512 + tiles - 1) / tiles;
+    if (groups > n_rows) groups = n_rows;
+    const int rows_per_block = (int)((n_rows + groups - 1) / groups);
+    const int gz = (n_rows + rows_per_block - 1) / rows_per_block;
+    SVCMI_LAUNCH(sweep_sample_prior_kernel, dim3(gx, gy, gz), dim3(TPB), 0, stream, stats, lds, noise_ncl, length, z, ldz, n_rows,
+                 rows_per_block, t, i);
     return SVCMI_LAST_ERROR();
 }

@@ -5,6 +5,7 @@
 #include "svcmi_rt.h"
 #include "../../include/svcmi.h"
 #include "pitch_coarse.h"
+#include "prior_sample.h"
 
 namespace {
 
@@ -146,8 +147,7 @@ __global__ __launch_bounds__(TPB) void sample_prior_kernel(const float* stats, i
         int tt = t0 + k, c = c0 + tx;
         if (tt < t && c < ic) {
             const float* sp = stats + ((long long)b * t + tt) * lds_;
-            float v = sp[c] + tile[tx][k] * expf(sp[ic + c]);
-            z[((long long)b * t + tt) * ldz + c] = tt < len ? v : 0.f;
+            prior_sample_store(z + ((long long)b * t + tt) * ldz + c, sp[c], tile[tx][k], prior_scale(sp[ic + c]), tt < len);
         }
     }
 }

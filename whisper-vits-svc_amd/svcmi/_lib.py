@@ -168,6 +168,16 @@ class SweepIO(Structure):
                 ("stream_frames", c_int32), ("wave", c_void_p), ("pit_k", c_void_p)]
 
 
+SINGERS_MAX = 32                   # SVCMI_SINGERS_MAX
+
+
+class SingersIO(Structure):
+    """svcmi_singers_io"""
+    _fields_ = [("ppg", c_void_p), ("vec", c_void_p), ("pit", c_void_p), ("length", c_void_p), ("source", c_void_p), ("spk", c_void_p),
+                ("noise", c_void_p), ("ppg_row_shift", c_int32), ("t", c_int32), ("n_singers", c_int32), ("stream_frames", c_int32),
+                ("wave", c_void_p), ("z_p", c_void_p)]
+
+
 class LstmLayer(Structure):
     """svcmi_lstm_layer"""
     _fields_ = [("ih", Weight), ("lin", Weight), ("whh", c_void_p), ("reserved", c_void_p)]
@@ -367,6 +377,10 @@ SIGNATURES = {
     "svcmi_sweep_io_bytes": (c_int64, []),
     "svcmi_synth_sweep_workspace_bytes": (c_int64, [POINTER(SynthModel), _I, _I, _I]),
     "svcmi_synth_sweep_fwd": (c_int, [POINTER(SynthModel), POINTER(SweepIO), _P, _L, _P]),
+    "svcmi_sweep_sample_prior_f32": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "svcmi_singers_io_bytes": (c_int64, []),
+    "svcmi_synth_singers_workspace_bytes": (c_int64, [POINTER(SynthModel), _I, _I, _I]),
+    "svcmi_synth_singers_fwd": (c_int, [POINTER(SynthModel), POINTER(SingersIO), _P, _L, _P]),
     "svcmi_trace_begin": (c_int, [_I]),
     "svcmi_trace_end": (c_int, [POINTER(TraceRecord), _I]),
     "svcmi_trace_op_name": (c_char_p, [_I]),
@@ -412,6 +426,8 @@ def load_library(path=None):
         raise SvcmiError(f"struct layout mismatch: svcmi_yin_plan is {lib.svcmi_yin_plan_bytes()} bytes in the library, {_c.sizeof(YinPlan)} in the binding")
     if lib.svcmi_sweep_io_bytes() != _c.sizeof(SweepIO):
         raise SvcmiError(f"struct layout mismatch: svcmi_sweep_io is {lib.svcmi_sweep_io_bytes()} bytes in the library, {_c.sizeof(SweepIO)} in the binding")
+    if lib.svcmi_singers_io_bytes() != _c.sizeof(SingersIO):
+        raise SvcmiError(f"struct layout mismatch: svcmi_singers_io is {lib.svcmi_singers_io_bytes()} bytes in the library, {_c.sizeof(SingersIO)} in the binding")
     if lib.svcmi_swipe_plan_bytes() != _c.sizeof(SwipePlan):
         raise SvcmiError(f"struct layout mismatch: svcmi_swipe_plan is {lib.svcmi_swipe_plan_bytes()} bytes in the library, {_c.sizeof(SwipePlan)} in the binding")
     return lib

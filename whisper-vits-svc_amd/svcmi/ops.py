@@ -358,6 +358,53 @@ class Ops:
         self._stage_call("svcmi_synth_sweep_fwd", ctypes.byref(m), ctypes.byref(io), ws, ws_bytes, self._stream())
         return (wave, pit_k) if want_pit else wave
 
+    # ------------------------------------------------------------------ singer sweep (csrc/sweep.hip, svcmi_synth_singers_fwd)
+    def sweep_sample_prior(self, stats, noise, length):
+        """stats [T, >= 2*I] (m | logs of ONE clip, a row-strided view is fine), noise [S, I, T] (the reference's randn_like(m) layout),
+        length int32 [1] (or None) -> z [S, T, I] = (m + noise * exp(logs)) * mask: the bits of ``sample_prior`` on S copies of stats."""
+        self._chk(stats, noise, length)
+        if noise.dim() != 3 or stats.dim() != 2:
+            raise SvcmiError(f"sweep_sample_prior: stats {tuple(stats.shape)}, noise {tuple(noise.shape)} do not fit")
+        S, I, T = noise.shape
+        if stats.shape[0] != T or stats.shape[1] < 2 * I or stats.stride(1) != 1 or not noise.is_contiguous():
+            raise SvcmiError(f"sweep_sample_prior: stats {tuple(stats.shape)}, noise {tuple(noise.shape)} do not fit")
+        if S > _lib.SINGERS_MAX:
+            raise SvcmiError(f"a singer sweep takes at most {_lib.SINGERS_MAX} singers per call, got {S}")
+        z = torch.empty(S, T, I, dtype=torch.float32, device=stats.device)
+        self._call("svcmi_sweep_sample_prior_f32", _ptr(stats), stats.stride(0), _ptr(noise), _ptr(length), _ptr(z), I, S, T, I, self._stream())
+        return z
+
+    def synth_singers_workspace_bytes(self, cm, n_singers, t, stream_frames=0):
+        return int(self.lib.svcmi_synth_singers_workspace_bytes(ctypes.byref(cm.struct), int(n_singers), int(t), int(stream_frames)))
+
+    def synth_singers_fwd(self, cm, ppg, vec, pit, spks, length, source, noise, *, ppg_row_shift=0, stream_frames=0, want_parts=False):
+        """One chunk in S timbres as ONE call (svcmi_synth_singers_fwd).  Batch-1 inputs: ppg [T >> shift, ppg_dim], vec [T, vec_dim],
+        pit [T], length int32 [1], source [T*hop] (ONE harmonic source for all singers); per singer: spks [S, spk_dim],
+        noise [S, inter, T] -> wave [S, 1, T*hop] (+ time-major z_p [S, T, inter] with ``want_parts``)."""
+        self._chk(ppg, vec, pit, spks, length, source, noise)
+        m = cm.struct
+        m.lp_min_flops = max(float(self.lp_min_flops), 1e-30)
+        T = pit.shape[0]
+        S = spks.shape[0] if spks.dim() == 2 else 0
+        if not 1 <= S <= _lib.SINGERS_MAX:
+            raise SvcmiError(f"a singer sweep takes 1..{_lib.SINGERS_MAX} speaker rows per call, got {tuple(spks.shape)}")
+        for t_, shape in ((ppg, ((T + (1 << ppg_row_shift) - 1) >> ppg_row_shift, m.ppg_dim)), (vec, (T, m.vec_dim)), (pit, (T,)), (spks, (S, m.spk_dim)),
+                          (length, (1,)), (source, (T * m.hop,)), (noise, (S, m.inter, T))):
+            if tuple(t_.shape) != shape or not t_.is_contiguous():
+                raise SvcmiError(f"expected a contiguous tensor of shape {shape}, got {tuple(t_.shape)}")
+        need = self.lib.svcmi_synth_singers_workspace_bytes(ctypes.byref(m), S, T, int(stream_frames))
+        if need < 0:
+            raise SvcmiError(f"svcmi_synth_singers_workspace_bytes failed with code {need}")
+        ws, ws_bytes = self.stage_workspace(need, pit.device)
+        io = _lib.SingersIO()
+        io.ppg, io.vec, io.pit, io.length, io.source, io.spk, io.noise = (_ptr(t_) for t_ in (ppg, vec, pit, length, source, spks, noise))
+        io.ppg_row_shift, io.t, io.n_singers, io.stream_frames = int(ppg_row_shift), T, S, int(stream_frames)
+        wave = torch.empty(S, 1, T * m.hop, dtype=torch.float32, device=pit.device)
+        z_p = torch.empty(S, T, m.inter, dtype=torch.float32, device=pit.device) if want_parts else None
+        io.wave, io.z_p = _ptr(wave), _ptr(z_p)
+        self._stage_call("svcmi_synth_singers_fwd", ctypes.byref(m), ctypes.byref(io), ws, ws_bytes, self._stream())
+        return (wave, z_p) if want_parts else wave
+
     def trace_begin(self, max_records=8192):
         """Per-launch timing of everything launched from here on (stage entry points: HIP events inside the C host; single-op calls of
         this class: torch events): bench.py's roofline leg."""

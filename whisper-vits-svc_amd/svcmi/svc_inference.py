@@ -192,6 +192,56 @@ def svc_infer_sweep(model, retrieval, spk, pit, ppg, vec, hp, device, shifts, no
     return outs if return_tensor else [o.cpu().numpy() for o in outs]
 
 
+SINGER_BATCH = 16             # singers per stage call of svc_infer_singers (profiles/singer_sweep.md)
+
+
+@torch.no_grad()
+def svc_infer_singers(model, retrieval, spks, pit, ppg, vec, hp, device, noise=None, singer_batch=SINGER_BATCH, return_tensor=False):
+    """One clip in S timbres: what a loop of ``svc_infer`` calls over the rows of ``spks`` [S, spk_dim] renders, as batches over the
+    singers.  Other arguments as ``svc_infer``.  Nothing up to the prior statistics reads the speaker, so per chunk the retrieval blend
+    runs once, the whole prior encoder once per group of ``singer_batch`` singers (at most 32), and only the reverse flow and the
+    generator run at batch; ``pitch2source`` runs once for the clip.  The chunk schedule is ``svc_infer``'s.
+    ``noise``: {"rand_ini": [1,11], "src_noise": [1,L,11], "enc_noises": [[S,1,inter,len_i] per chunk]}: the source draws are shared,
+    the prior draws are per singer (default: fresh draws).  The one deliberate difference from the loop: every singer hears the SAME
+    NSF excitation (one rand_ini, one noise) where the loop would draw a new one per call -- a valid draw for each of them, and the
+    fairer comparison between voices.  Returns a list of S np.float32 [hop*T - 1] (device tensors with ``return_tensor``)."""
+    from ._lib import SINGERS_MAX
+    if spks.dim() != 2 or spks.shape[0] < 1:
+        raise ValueError(f"svc_infer_singers: spks must be [S, spk_dim] with S >= 1, got {tuple(spks.shape)}")
+    S, singer_batch = spks.shape[0], int(singer_batch)
+    if not 1 <= singer_batch <= SINGERS_MAX:
+        raise ValueError(f"svc_infer_singers: singer_batch must be in 1..{SINGERS_MAX}, got {singer_batch}")
+    dev = torch.device(device)
+    n = min(pit.shape[0], vec.shape[0], ppg.shape[0])
+    pit = pit[:n].to(dev, torch.float32)
+    vec = vec[:n].to(dev, torch.float32)
+    ppg = ppg[:n].to(dev, torch.float32)
+    spks = spks.to(dev, torch.float32)
+    src_noise = None if noise is None else (noise["rand_ini"], noise["src_noise"])
+    source = model.pitch2source(pit.unsqueeze(0), noise=src_noise)                         # [1, 1, hop * n]: once, for every singer
+    hop = hp.data.hop_length
+    retrieval = retrieval if retrieval is not None else DummyRetrieval()
+    passthrough = isinstance(retrieval, DummyRetrieval)
+    groups = [(g, min(g + singer_batch, S)) for g in range(0, S, singer_batch)]
+    pieces = [[] for _ in range(S)]
+    for i, (cs, ce, cso, ceo) in enumerate(chunk_schedule(n, hop)):
+        sub_ppg, sub_vec = ppg[cs:ce], vec[cs:ce]
+        if getattr(retrieval, "on_device", False):
+            sub_ppg, sub_vec = retrieval.retriv_whisper(sub_ppg), retrieval.retriv_hubert(sub_vec)
+        elif not passthrough:
+            sub_ppg = retrieval.retriv_whisper(sub_ppg.cpu()).to(dev)
+            sub_vec = retrieval.retriv_hubert(sub_vec.cpu()).to(dev)
+        sub_len = torch.tensor([ce - cs], dtype=torch.int64)
+        enc_noise = None if noise is None else noise["enc_noises"][i].reshape(S, -1, ce - cs)
+        for a, b in groups:
+            sub_out = model.inference_singers(sub_ppg.unsqueeze(0), sub_vec.unsqueeze(0), pit[cs:ce].unsqueeze(0), spks[a:b], sub_len,
+                                              source[:, :, cs * hop:ce * hop], noise=None if enc_noise is None else enc_noise[a:b])
+            for k in range(a, b):
+                pieces[k].append(sub_out[k - a, 0, cso:ceo])
+    outs = [torch.cat(p) for p in pieces]
+    return outs if return_tensor else [o.cpu().numpy() for o in outs]
+
+
 F0_METHODS = ("crepe", "salience", "pyin")
 F0_CHOICES = F0_METHODS + ("swipe",)       # what --f0 and extract_features take (F0_METHODS keeps the value its users pin)
 

@@ -72,6 +72,19 @@ def mix_speakers(eva_conf, save_path=None, dim=256):
     return eva
 
 
+def mix_speaker_rows(spks, weights):
+    """svc_eva.py:15-19 on arrays: ``spks`` as ``np.load`` gives them, ``weights`` the Python floats of ``eva_conf``, in the given order.
+    The expression is the reference's own (for a float32 row and a Python float numpy forms the product in float32 and the sum in
+    float64), so the result holds the bits of ``mix_speakers`` on the same arrays saved to files.  -> np.float64 [dim]"""
+    spks, weights = list(spks), list(weights)
+    if not spks or len(spks) != len(weights):
+        raise ValueError(f"mix_speaker_rows: {len(spks)} embeddings, {len(weights)} weights")
+    eva = np.zeros(len(spks[0]))
+    for spk, weight in zip(spks, weights):
+        eva = eva + spk * weight
+    return eva
+
+
 def _main_export(argv=None):
     import argparse
     from .svc_inference import load_config

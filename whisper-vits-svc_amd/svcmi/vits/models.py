@@ -213,6 +213,30 @@ class SynthesizerInfer:
         return ops.synth_sweep_fwd(self._cmodel(), ppg, vec, pit, spk, length, sources, noise, factors, stream_frames=self.stream_frames or 0)
 
     @torch.no_grad()
+    def inference_singers(self, ppg, vec, pit, spks, ppg_l, source, noise=None, return_parts=False):
+        """``inference`` of ONE clip in S timbres: ppg [1,T,ppg_dim], vec [1,T,vec_dim], pit [1,T] Hz, spks [S,spk_dim], ppg_l int64 [1],
+        source [1,1,hop*T] (ONE harmonic source, heard by every singer) -> waveforms [S,1,hop*T].  Nothing up to the prior statistics
+        reads the speaker: the prior encoder runs once, flow and generator at batch S.  ``noise`` [S,inter,T]: the randn_like(m) of each
+        singer (default: fresh draws per singer).  With ``return_parts`` also {"z_p": [S,inter,T]} in the layout of ``inference``."""
+        w, ops, dev = self._weights(), self.ops, self._device
+        if ppg.shape[0] != 1 or pit.shape[0] != 1 or spks.dim() != 2:
+            raise ValueError("inference_singers takes one clip (batch 1) and speaker rows [S, spk_dim]")
+        S, T = spks.shape[0], ppg.shape[1]
+        ppg, vec, pit = (t.to(dev, torch.float32).contiguous()[0] for t in (ppg, vec, pit))
+        spks = spks.to(dev, torch.float32).contiguous()
+        length = ppg_l.to(dev, torch.int32).contiguous().view(1)
+        source = source.to(dev, torch.float32).contiguous().view(T * w.hop)
+        if noise is None:
+            noise = torch.randn(S, w.I, T, device=dev)
+        noise = noise.to(dev, torch.float32).contiguous()
+        out = ops.synth_singers_fwd(self._cmodel(), ppg, vec, pit, spks, length, source, noise, stream_frames=self.stream_frames or 0,
+                                    want_parts=return_parts)
+        if return_parts:
+            o, z_p = out
+            return o, {"z_p": ops.nlc_to_ncl(z_p)}
+        return out
+
+    @torch.no_grad()
     def inference_ppg50(self, ppg50, vec, pit, spk, lengths, source, noise=None):
         """Same as ``inference`` but takes the Whisper PPG at its native 50 fps ([B, ceil(T/2), ppg_dim], may be a batch-strided view of
         the encoder output) and fuses the ``np.repeat(ppg, 2, 0)`` of svc_inference.py:175-177 into the first conv's loads.  All
